@@ -11,8 +11,15 @@ Multi-GPU (torchrun): instances are independent, so each rank owns its own batch
 data-path collective); only the timing max-reduction crosses ranks.
 
 Prints ONE JSON line on rank 0 with the roofline of the shooting kernel (achieved algorithmic HBM GB/s
-from HIP events on the launch stream vs 8 TB/s) and the CPU baseline (the plain-C oracle port of the
-as-written reference evaluation, OpenMP, timed on a bounded sample on this host).
+from HIP events on the launch stream vs 8 TB/s).
+
+A plain run (``bench.py --gpus 1 --steps K --warmup W``) does only what the headline needs: set up, settle, W warmup
+steps, K timed steps, the result line.  ``--dump-outputs DIR`` adds ``DIR/g.npy`` and ``DIR/jac.npy``: what the last
+timed step left in the caller's g and J_g buffers (float64), for a fixed seeded sample of instances when the batch
+is larger than the sample.  ``--full`` adds every other section to the line: the CPU baseline (the plain-C oracle port
+of the as-written reference evaluation, OpenMP, timed on a bounded sample on this host), the kept-constants launch,
+cfg 3 / 4 / 5, collocation, IVP, wall-clock to convergence and the reaching task; the ``--no-*``, ``--cpu-seconds``
+and ``--nmpc-horizons`` options select among them.
 """
 
 from __future__ import annotations
@@ -41,6 +48,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=1 << 20, help="instances per GPU")
     ap.add_argument("--settle", type=float, default=0.3,
                     help="seconds of untimed launches before the warmup steps (power-management transient, DESIGN.md)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other section (CPU baselines, kept-constants launch, "
+                         "cfg 3 / 4 / 5, collocation, IVP, convergence, reaching task); off: those keys are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (g, J_g values; a seeded sample of instances of a "
+                         "large batch) as DIR/g.npy and DIR/jac.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline sample budget (0: skip)")
     ap.add_argument("--no-solve", action="store_true", help="skip the wall-clock-to-convergence section")
     ap.add_argument("--no-msk", action="store_true", help="skip the cfg-5 musculoskeletal section")
@@ -77,6 +90,28 @@ def to_tiled(a):
     """(len, B) SoA -> CFX_LAYOUT_TILED64 (B / 64, len, 64): element e of instance b at ((b/64) len + e) 64 + b%64."""
     n, B = a.shape
     return a.T.reshape(B // 64, 64, n).transpose(1, 2).contiguous()
+
+
+DUMP_INSTANCES = 1 << 15  # 32,768 instances of cfg 2: g 10.5 MB + J_g 26.2 MB in float64
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, g, jac, B):
+    """--dump-outputs: the headline step's outputs as the caller receives them, instance-major — g.npy (n, ng) and
+    jac.npy (n, nnz_jac), float64 — for all B instances when B <= DUMP_INSTANCES, else for DUMP_INSTANCES of them
+    drawn without replacement by numpy's default_rng(DUMP_SEED) (sorted; the same instances for the same B)."""
+    import torch
+
+    if B <= DUMP_INSTANCES:
+        idx = np.arange(B)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, DUMP_INSTANCES, replace=False))
+    idx = torch.from_numpy(idx).to(g.device)
+    tile, lane = idx // 64, idx % 64
+    out = pathlib.Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in (("g", g), ("jac", jac)):  # CFX_LAYOUT_TILED64 (B / 64, len, 64) -> (n, len)
+        np.save(out / f"{name}.npy", a[tile, :, lane].cpu().numpy().astype(np.float64, copy=False))
 
 
 def pmc_traffic():
@@ -822,23 +857,29 @@ def main():
     bytes_per_instance = 8 * (h.nv + h.ng + h.nnz_jac)  # read v, write g and J_g values
     achieved = bytes_per_instance * B / (kern_ms * 1e-3) / 1e9
     traffic = pmc_traffic()
+    if args.dump_outputs and rank == 0:  # before any other section touches the buffers
+        dump_outputs(args.dump_outputs, g, jac, B)
 
-    kept = keep_constant_section(h, v, g, jac) if (world == 1 and not args.no_solve) else None
-    msk_tp, msk_ocp = msk_throughput(local, dist, world, rank, args.backend) if not args.no_msk else (None, None)
+    # everything below the headline runs under --full only
+    full = args.full
+    solve = full and not args.no_solve
+    kept = keep_constant_section(h, v, g, jac) if (world == 1 and solve) else None
+    msk_tp, msk_ocp = msk_throughput(local, dist, world, rank, args.backend) if (full and not args.no_msk) \
+        else (None, None)
     # cfg 4 on every rank (scenarios shard; weak scaling)
     nm = nmpc_section(local, args.nmpc_horizons, dist, world, rank, args.backend) \
-        if (not args.no_solve and args.nmpc_horizons) else None
+        if (solve and args.nmpc_horizons) else None
 
     out = None
     if rank == 0:
-        cpu = cpu_baseline(ocp, args.cpu_seconds) if (world == 1 and args.cpu_seconds > 0) else None
-        conv = convergence(local) if (world == 1 and not args.no_solve) else None
-        ivp = ivp_section(local) if (world == 1 and not args.no_solve) else None
-        col = collocation_section(local) if (world == 1 and not args.no_solve) else None
-        c3 = cfg3_section(local, args.cpu_seconds / 4) if (world == 1 and not args.no_solve) else None
-        reach = reaching_section(local) if (world == 1 and not args.no_solve and not args.no_reaching) else None
+        cpu = cpu_baseline(ocp, args.cpu_seconds) if (full and world == 1 and args.cpu_seconds > 0) else None
+        conv = convergence(local) if (world == 1 and solve) else None
+        ivp = ivp_section(local) if (world == 1 and solve) else None
+        col = collocation_section(local) if (world == 1 and solve) else None
+        c3 = cfg3_section(local, args.cpu_seconds / 4) if (world == 1 and solve) else None
+        reach = reaching_section(local) if (world == 1 and solve and not args.no_reaching) else None
         msk = msk_tp
-        if msk_tp is not None and world == 1 and not args.no_solve:
+        if msk_tp is not None and world == 1 and solve:
             msk = msk_section(local, msk_tp, msk_ocp, cpu_seconds=args.cpu_seconds / 2, multistart=not args.no_multistart)
         out = {
             "metric": METRIC,
@@ -847,6 +888,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(full),
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": "weak",

@@ -6,9 +6,9 @@
 #   tests            the whole -m gpu suite
 #   tests:EXPR       -m gpu tests selected by pytest -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (defaults) -> bench.json
-#   bench20          python bench.py --steps 20 --warmup 5 -> bench_k20.json
-#   prof             rocprofv3 --kernel-trace --stats of bench.py --steps 20
+#   bench            python bench.py --full (every section) -> bench.json
+#   bench20          python bench.py --steps 20 --warmup 5 (the plain run: headline only) -> bench_k20.json
+#   prof             rocprofv3 --kernel-trace --stats of bench.py --full --steps 20
 #   multistart:RUNS  scripts/msk_multistart_probe.py --native --runs RUNS (e.g. 64:0.1,512:0.1)
 #   specms:RUNS:SOFT the same with the BatchedIpm specification and soft_resto_pderror_reduction_factor SOFT
 #   py:SCRIPT[:ARGS] python SCRIPT ARGS (ARGS with commas for spaces), stdout to SCRIPT's name .txt
@@ -42,10 +42,10 @@ for step in "$@"; do
         tests:*) run 600 "pytest_${step#tests:}.log" python -u -m pytest tests -m gpu -x -v --timeout 300 \
                      --timeout-method thread -k "${step#tests:}" ;;
         smoke) run 300 smoke.log python -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) run 600 bench.log python bench.py && grep '^{' "$out/bench.log" | tail -n 1 > "$out/bench.json" ;;
+        bench) run 600 bench.log python bench.py --full && grep '^{' "$out/bench.log" | tail -n 1 > "$out/bench.json" ;;
         bench20) run 600 bench20.log python bench.py --steps 20 --warmup 5 &&
                  grep '^{' "$out/bench20.log" | tail -n 1 > "$out/bench_k20.json" ;;
-        prof) run 900 prof.log rocprofv3 --kernel-trace --stats -d "$out/prof" -o run -- python3 bench.py --steps 20 ;;
+        prof) run 900 prof.log rocprofv3 --kernel-trace --stats -d "$out/prof" -o run -- python3 bench.py --full --steps 20 ;;
         multistart:*) run 1100 "multistart_${step#multistart:}.log" python3 -u scripts/msk_multistart_probe.py --native \
                           --runs "${step#multistart:}" --jsonl "$out/multistart.jsonl" ;;
         specms:*) r=${step#specms:}

@@ -11,7 +11,7 @@ import pytest
 from oracle import fes_msk as M
 from tests import msk_cases as MC
 
-REF_MODELS = pathlib.Path("/root/reference/examples/msk_models")
+REF_MODELS = pathlib.Path(__file__).resolve().parent / "golden" / "msk_models"  # the reference's bioMod files, as data
 FIXTURES = ("arm26_biceps_triceps", "arm26", "arm26_biceps", "arm26_biceps_1dof")
 
 
@@ -85,7 +85,6 @@ def test_oracle_muscle_torque_signs():
 
 # ---- fixtures and the product's bioMod reader -----------------------------------------------------------------
 
-@pytest.mark.skipif(not REF_MODELS.exists(), reason="reference bioMod files not present")
 @pytest.mark.parametrize("name", FIXTURES)
 def test_fixture_and_product_parser_match_the_reference_files(name):
     from cocofest_amd.msk import parse_biomod
