@@ -1687,7 +1687,7 @@ template <int NQ, int NM, int FAM>
 __global__ void __launch_bounds__(256) k_msk_hproj(const MskParams P, const double* __restrict__ TS,
                                                    const double* __restrict__ GQ, int ntasks, double* __restrict__ H) {
     constexpr int NX = NM * msk_nxm<FAM>() + 2 * NQ;
-    constexpr int NZ = NX + (msk_pw<FAM>() ? NM : 0) + NQ;  // upper bound of nz
+    constexpr int NZ = NX + msk_numax<NQ, NM, FAM>();  // upper bound of nz (the Hmed intensities included)
     const int64_t B = P.B;
     const int nz = P.nz, Q = P.Q;
     const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2040,7 +2040,7 @@ __global__ void __launch_bounds__(256) k_msk_hproj_stage(const MskParams P, cons
                                                          const double* __restrict__ GQ, int ntasks,
                                                          double* __restrict__ HQ) {
     constexpr int NX = NM * msk_nxm<FAM>() + 2 * NQ;
-    constexpr int NZ = NX + (msk_pw<FAM>() ? NM : 0) + NQ;
+    constexpr int NZ = NX + msk_numax<NQ, NM, FAM>();
     const int64_t B = P.B;
     const int nz = P.nz;
     const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2093,7 +2093,7 @@ __global__ void __launch_bounds__(kMskHpS * kMskMaxZ) k_msk_hproj_stage_lds(cons
                                                                             const double* __restrict__ GQ, int ntasks,
                                                                             double* __restrict__ HQ) {
     constexpr int NX = NM * msk_nxm<FAM>() + 2 * NQ;
-    constexpr int NZ = NX + (msk_pw<FAM>() ? NM : 0) + NQ;
+    constexpr int NZ = NX + msk_numax<NQ, NM, FAM>();
     extern __shared__ double sh[];  // [kMskHpS][ntasks] G, then [kMskHpS][NX nz] T
     const int64_t B = P.B;
     const int nz = P.nz;

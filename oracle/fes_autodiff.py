@@ -24,8 +24,9 @@ differentiates the same recursion twice with no step size, so the second-order r
 is taken: "fr" forward-over-reverse (default), "ff" forward-over-forward, "rr" reverse-over-reverse; the gap between
 "ff" and "rr" is the reference's own rounding noise (tests/test_autodiff_oracle.py measures it).
 
-Musculoskeletal problems are out of scope: their oracle (``fes_msk``) is rigid-body dynamics and muscle geometry, and
-restating that in torch is a piece of work of its own.  They keep the finite-difference reference.
+Musculoskeletal problems are out of scope of this module: their oracle (``fes_msk``: rigid-body dynamics and muscle
+geometry) is restated in ``msk_autodiff``, which reuses ``rhs`` (its ``fl`` / ``fv`` / ``fp`` / ``legacy`` arguments
+exist for it; the defaults leave every result here bit-identical) and ``_step`` from this module.
 """
 
 from __future__ import annotations
@@ -49,13 +50,21 @@ def _t(a):
 # --------------------------------------------------------------------------------------
 
 
-def cn_sum(c, t, row, lam=None):
-    """ding2003.py:200-252 (ri_fun, exp_time_fun, cn_sum_fun); r0 = km_rest + 1.04 (268-272)."""
+def cn_sum(c, t, row, lam=None, legacy_skip_first=False):
+    """ding2003.py:200-252 (ri_fun, exp_time_fun, cn_sum_fun); r0 = km_rest + 1.04 (268-272).
+    ``legacy_skip_first`` as fes_oracle.cn_sum: once a window holds more than one real pulse its first term is left
+    out (a 0 / 1 weight computed from the row, so that vmap goes through)."""
     r0 = c["km_rest"] + c["r0_km_relationship"]
     total = 0.0
-    for i in range(row.shape[-1]):
+    T = row.shape[-1]
+    if legacy_skip_first:
+        n_real = (row > -1e6).sum(dim=-1, keepdim=True)
+        keep = torch.where((torch.arange(T) == T - n_real) & (n_real > 1), 0.0, 1.0).to(F64)
+    for i in range(T):
         ri = 1.0 if i == 0 else 1 + (r0 - 1) * torch.exp(-(row[..., i] - row[..., i - 1]) / c["tauc"])
         term = ri * torch.exp(-(t - row[..., i]) / c["tauc"])
+        if legacy_skip_first:
+            term = term * keep[..., i]
         total = total + (term if lam is None else term * lam[i])
     return total
 
@@ -70,15 +79,17 @@ def a_calculation(c, a_scale, pulse_width):
     return a_scale * (1 - torch.exp(-(pulse_width - c["pd0"]) / c["pdt"]))
 
 
-def rhs(name, c, t, x, u, row):
+def rhs(name, c, t, x, u, row, fl=1.0, fv=1.0, fp=0.0, legacy=False):
     """system_dynamics of the six models: ding2003.py:153-198, ding2003_with_fatigue.py:138-240,
-    ding2007.py:121-170, ding2007_with_fatigue.py:133-241, hmed2018.py:119-167, hmed2018_with_fatigue.py:124-229."""
+    ding2007.py:121-170, ding2007_with_fatigue.py:133-241, hmed2018.py:119-167, hmed2018_with_fatigue.py:124-229.
+    ``fl`` / ``fv`` / ``fp``: the Hill coefficients of the musculoskeletal model (1, 1, 0 without one); ``legacy``: the
+    stored reaching-task revision's conventions, both as fes_oracle.rhs."""
     fatigue = name.endswith("with_fatigue")
     cn, f = x[0], x[1]
     lam = None
     if name.startswith("hmed2018"):
         lam = [lambda_i(c, u[i]) for i in range(row.shape[-1])]
-    cs = cn_sum(c, t, row, lam)
+    cs = cn_sum(dict(c, km_rest=x[4]) if (legacy and fatigue) else c, t, row, lam, legacy)
     cn_dot = (1 / c["tauc"]) * cs - (cn / c["tauc"])  # ding2003.py:254-266
     if fatigue:
         a, tau1, km = x[2], x[3], x[4]
@@ -88,7 +99,8 @@ def rhs(name, c, t, x, u, row):
     if name.startswith("ding2007"):
         a = a_calculation(c, a, u[0])
     s = cn / (km + cn)
-    f_dot = a * s - (f / (tau1 + c["tau2"] * s))  # ding2003.py:274-311 (force-length/velocity factors are 1)
+    # ding2003.py:274-311; with the defaults the factor is the float 1.0 and the product is exact
+    f_dot = (a * s - (f / (tau1 + c["tau2"] * s))) * (fl * fv + fp)
     parts = [cn_dot, f_dot]
     if fatigue:
         a_rest = c["a_scale"] if name.startswith("ding2007") else c["a_rest"]
