@@ -15,7 +15,7 @@ import numpy as np
 
 LIB_PATH = pathlib.Path(__file__).with_name("libcfx.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 OK, EINVAL, EHIP, ENOMEM, EUNSUPPORTED, ENODEV, ECALLBACK = 0, -1, -2, -3, -4, -5, -6
 MODEL_IDS = {
     "ding2003": 0,
@@ -34,6 +34,10 @@ OBJ_LAGRANGE, OBJ_MAYER, OBJ_MAYER_INV = 0, 1, 2
 MSK_FORCE_LENGTH, MSK_FORCE_VELOCITY, MSK_PASSIVE_FORCE, MSK_RESIDUAL_TORQUE = 1, 2, 4, 8
 MSK_PULSE_WIDTH_PER_PULSE, MSK_LEGACY_CALCIUM = 16, 32
 VAR_STATE, VAR_CONTROL = 0, 1
+# identified-parameter ids (CFX_P_*), by the models' identifiable_parameters keys
+PARAM_IDS = {"a_rest": 0, "km_rest": 1, "tau1_rest": 2, "tau2": 3, "a_scale": 4, "pd0": 5, "pdt": 6, "ar": 7, "bs": 8,
+             "Is": 9, "cr": 10}
+ID_MAX_PARAMS = 8
 
 
 class CfxError(RuntimeError):
@@ -191,6 +195,10 @@ SIGNATURES = {
     "cfx_eval_all": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32]),
     "cfx_eval_all_h": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint32]),
     "cfx_integrate": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
+    "cfx_id_check": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "cfx_id_forces": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, C.c_int64, _P, _P, C.c_uint32]),
+    "cfx_id_normal": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, _P, C.c_int64, _P, _P, _P,
+                                C.c_uint32]),
     "cfx_msk_create": (C.c_int, [C.POINTER(MskProblem), C.POINTER(_P)]),
     "cfx_band_lu": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32, _P, _P]),
     "cfx_band_lu_solve": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, _P, _P, C.c_int32, _P, _P]),
@@ -427,7 +435,7 @@ class Handle:
         return r, c
 
     # ---- evaluation ----
-    def _buffers(self, *slots):
+    def _buffers(self, *slots, total=False):
         """Check every buffer of one call against its slot before libcfx sees it; return (buffers, flags).
 
         ``slots``: (name, buffer or None, per-instance length, is_output).  libcfx reads / writes exactly
@@ -441,7 +449,7 @@ class Handle:
             if a is None:
                 out.append(None)
                 continue
-            want = self.batch * n
+            want = n if total else self.batch * n  # total: n counts the whole buffer
             if _is_tensor(a):
                 if not a.is_cuda:
                     raise CfxError(EINVAL, f"{name}: CPU tensor; pass a numpy array (host) or a CUDA tensor (device)")
@@ -550,6 +558,64 @@ class Handle:
         self._torch_stream(fl)
         self._check(self.lib.cfx_integrate(self.h, _ptr(x0), _ptr(u), _ptr(traj), fl))
         return traj
+
+    # ---- force-parameter identification (always SoA buffers: (rows, instances)) ----
+    def _id_buffers(self, slots):
+        """``_buffers`` for the identification calls: a slot's length is its total count of doubles (the experiment
+        data are shared, n_data = 1, or per instance)."""
+        return self._buffers(*slots, total=True)
+
+    def _id_args(self, param_ids, n_data):
+        ids = np.ascontiguousarray(param_ids, dtype=np.int32).reshape(-1)
+        if n_data not in (1, self.batch):
+            raise CfxError(EINVAL, f"n_data = {n_data}: must be 1 or the batch size {self.batch}")
+        return ids, ids.ctypes.data_as(C.POINTER(C.c_int32)), ids.size
+
+    def id_forces(self, param_ids, theta, u=None, n_data=1, force=None, sens=None, with_sens=False):
+        """cfx_id_forces: node forces (N+1, B) and, with ``with_sens`` or a ``sens`` buffer, dF_k / dtheta_j
+        (N+1, n_id, B) for per-instance parameters theta (n_id, B).  Returns (force, sens or None)."""
+        ids, idp, n_id = self._id_args(param_ids, n_data)
+        N, B = self.n_shooting, self.batch
+        if _is_tensor(theta):
+            import torch
+
+            new = lambda *sh: torch.empty(sh, dtype=torch.float64, device=theta.device)  # noqa: E731
+        else:
+            new = lambda *sh: np.empty(sh)  # noqa: E731
+        force = new(N + 1, B) if force is None else force
+        if sens is None and with_sens:
+            sens = new(N + 1, n_id, B)
+        (theta, u, force, sens), fl = self._id_buffers([
+            ("theta", theta, n_id * B, False), ("u", u if self.nu else None, N * self.nu * n_data, False),
+            ("force", force, (N + 1) * B, True), ("sens", sens, (N + 1) * n_id * B, True)])
+        self._torch_stream(fl)
+        self._check(self.lib.cfx_id_forces(self.h, n_id, idp, _ptr(theta), _ptr(u), n_data, _ptr(force), _ptr(sens),
+                                           fl))
+        return force, sens
+
+    def id_normal(self, param_ids, theta, target, weight, u=None, n_data=1, cost=None, grad=None, gn=None):
+        """cfx_id_normal: cost (B,), grad (n_id, B) and the packed lower triangle of the Gauss-Newton matrix
+        (n_id (n_id + 1) / 2, B) of the weighted least-squares fit to target / weight (N+1, n_data)."""
+        ids, idp, n_id = self._id_args(param_ids, n_data)
+        N, B = self.n_shooting, self.batch
+        npk = n_id * (n_id + 1) // 2
+        if _is_tensor(theta):
+            import torch
+
+            new = lambda *sh: torch.empty(sh, dtype=torch.float64, device=theta.device)  # noqa: E731
+        else:
+            new = lambda *sh: np.empty(sh)  # noqa: E731
+        cost = new(B) if cost is None else cost
+        grad = new(n_id, B) if grad is None else grad
+        gn = new(npk, B) if gn is None else gn
+        (theta, u, target, weight, cost, grad, gn), fl = self._id_buffers([
+            ("theta", theta, n_id * B, False), ("u", u if self.nu else None, N * self.nu * n_data, False),
+            ("target", target, (N + 1) * n_data, False), ("weight", weight, (N + 1) * n_data, False),
+            ("cost", cost, B, True), ("grad", grad, n_id * B, True), ("gn", gn, npk * B, True)])
+        self._torch_stream(fl)
+        self._check(self.lib.cfx_id_normal(self.h, n_id, idp, _ptr(theta), _ptr(u), _ptr(target), _ptr(weight),
+                                           n_data, _ptr(cost), _ptr(grad), _ptr(gn), fl))
+        return cost, grad, gn
 
     def synchronize(self):
         self._check(self.lib.cfx_synchronize(self.h))

@@ -12,6 +12,7 @@
 #include "../../include/cfx.h"
 #include "cfx_aux.h"
 #include "cfx_colloc.h"
+#include "cfx_ident.h"
 #include "cfx_internal.h"
 #include "cfx_launch.h"
 #include "cfx_msk_launch.h"
@@ -77,6 +78,10 @@ struct cfx_handle {
     int n_ties = 0;
     int64_t tie_row0 = 0, tie_j0 = 0;  // their first g row and J_g value
     double* d_cs1 = nullptr;       // CFX_MSK_LEGACY_CALCIUM: d cs / d Km per stage and muscle
+    // force-parameter identification (cfx_id_forces / cfx_id_normal): stimulation tables built on first use
+    double* d_id_tab = nullptr;
+    IdParams idp{};
+    DevBuf idbuf[9];
     DevBuf main[S_COUNT], stage[S_COUNT];
     std::string err;
 };
@@ -806,8 +811,10 @@ extern "C" void cfx_destroy(cfx_handle* h) {
     for (void* p : {(void*)h->d_tab, (void*)h->d_rest, (void*)h->d_cna, (void*)h->d_htasks, (void*)h->d_obj,
                     (void*)h->d_targets, (void*)h->d_sl_param, (void*)h->d_sl_joff, (void*)h->d_hdiag,
                     (void*)h->d_geom, (void*)h->d_mobj, (void*)h->d_msk_imin, (void*)h->d_mk, (void*)h->d_ties,
-                    (void*)h->d_cs1})
+                    (void*)h->d_cs1, (void*)h->d_id_tab})
         if (p) (void)hipFree(p);
+    for (DevBuf& b : h->idbuf)
+        if (b.p) (void)hipFree(b.p);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
 }
@@ -1083,6 +1090,280 @@ extern "C" int cfx_integrate(cfx_handle* h, const double* x0, const double* u, d
                                     : launch_ivp_ding(h->model, h->scheme, h->kp, X0, U, TR, h->stream);
     CFX_HIP(h, e);
     if ((rc = finish_out(h, S_OUT, TR, traj, nsamp * h->sz.nx, flags)) != CFX_OK) return rc;
+    return sync_if_host(h, flags);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// force-parameter identification (cfx_ident.h)
+// ------------------------------------------------------------------------------------------------------
+// canonical direction slot of a parameter id for a model (-1: not one of the model's parameters)
+static int id_slot(int model, int pid) {
+    const bool d03 = model == M_D03, d07 = model == M_D07, h18 = model == M_H18;
+    switch (pid) {
+        case CFX_P_A_REST: return d03 || h18 ? ID_A : -1;
+        case CFX_P_A_SCALE: return d07 ? ID_A : -1;
+        case CFX_P_KM_REST: return ID_KM;
+        case CFX_P_TAU1_REST: return ID_TAU1;
+        case CFX_P_TAU2: return ID_TAU2;
+        case CFX_P_PD0: return d07 ? ID_P4 : -1;
+        case CFX_P_PDT: return d07 ? ID_P5 : -1;
+        case CFX_P_AR: return h18 ? ID_P4 : -1;
+        case CFX_P_BS: return h18 ? ID_P5 : -1;
+        case CFX_P_IS: return h18 ? ID_P6 : -1;
+        case CFX_P_CR: return h18 ? ID_P7 : -1;
+        default: return -1;
+    }
+}
+
+// The parameter-list checks; col[slot] = column of the slot in theta (-1: not identified).
+static int id_check(int model, int32_t n_id, const int32_t* ids, int32_t* col, std::string& msg) {
+    if (model < CFX_DING2003 || model > CFX_HMED2018_FATIGUE) {
+        msg = "cfx_id: unknown model";
+        return CFX_EINVAL;
+    }
+    if (is_fatigue(model)) {
+        msg = "cfx_id: identification is not available for the fatigue models";
+        return CFX_EUNSUPPORTED;
+    }
+    if (n_id < 1 || n_id > CFX_ID_MAX_PARAMS) {
+        msg = "cfx_id: n_id must be in [1, 8]";
+        return CFX_EINVAL;
+    }
+    if (!ids) {
+        msg = "cfx_id: param_ids is NULL";
+        return CFX_EINVAL;
+    }
+    for (int s = 0; s < ID_SLOTS; ++s) col[s] = -1;
+    for (int j = 0; j < n_id; ++j) {
+        if (ids[j] < CFX_P_A_REST || ids[j] > CFX_P_CR) {
+            msg = "cfx_id: unknown parameter id " + std::to_string(ids[j]);
+            return CFX_EINVAL;
+        }
+        const int s = id_slot(model, ids[j]);
+        if (s < 0) {
+            msg = "cfx_id: parameter id " + std::to_string(ids[j]) + " is not a parameter of model " +
+                  std::to_string(model);
+            return CFX_EINVAL;
+        }
+        if (col[s] >= 0) {
+            msg = "cfx_id: duplicate parameter id " + std::to_string(ids[j]);
+            return CFX_EINVAL;
+        }
+        col[s] = j;
+    }
+    return CFX_OK;
+}
+
+extern "C" int cfx_id_check(int32_t model, int32_t n_id, const int32_t* param_ids) {
+    int32_t col[ID_SLOTS];
+    return id_check(model, n_id, param_ids, col, g_create_error);
+}
+
+// Stimulation tables of the identification kernels, built and uploaded on the first call (cfx_ident.h):
+// Ding c0 | c1 [N * Q] each; Hmed E [N * Q] | w0 | w1 [N * T] each.
+static int id_prepare(cfx_handle* h) {
+    if (h->d_id_tab) return CFX_OK;
+    const cfx_problem& p = h->prob;
+    const cfx_constants& c = p.constants;
+    const int N = p.n_shooting, m = p.n_steps, T = p.truncation, S = h->stages, Q = m * S;
+    const bool hmed = is_int(h->model);
+    const double dt = p.final_time / N, hh = dt / m;
+    const size_t nq = (size_t)N * Q, nt = (size_t)N * T;
+    std::vector<double> tab(hmed ? nq + 2 * nt : 2 * nq, 0.0);
+    std::vector<double> ei(T);
+    for (int k = 0; k < N; ++k) {
+        const double* row = &h->rows[(size_t)k * T];
+        for (int i = 0; i < T; ++i) ei[i] = i == 0 ? 0.0 : std::exp(-(row[i] - row[i - 1]) / c.tauc);
+        const double t0 = k * dt;
+        if (hmed)
+            for (int i = 0; i < T; ++i) {
+                const double w = std::exp(-(t0 - row[i]) / c.tauc);
+                tab[nq + k * (size_t)T + i] = w;
+                tab[nq + nt + k * (size_t)T + i] = ei[i] * w;
+            }
+        for (int j = 0; j < m; ++j) {
+            const double tj = t0 + j * hh;
+            for (int s = 0; s < S; ++s) {
+                double t = tj;  // stage times as build_tables
+                if (S == 2 && s == 1) t = tj + hh / 2;
+                if (S == 4 && (s == 1 || s == 2)) t = tj + hh / 2;
+                if (S == 4 && s == 3) t = tj + hh;
+                const size_t q = (size_t)k * Q + (size_t)j * S + s;
+                if (hmed) {
+                    tab[q] = std::exp(-(t - t0) / c.tauc);
+                } else {
+                    double s0 = 0.0, s1 = 0.0;
+                    for (int i = 0; i < T; ++i) {
+                        const double e = std::exp(-(t - row[i]) / c.tauc);
+                        s0 = s0 + e;
+                        s1 = s1 + ei[i] * e;
+                    }
+                    tab[q] = s0;
+                    tab[nq + q] = s1;
+                }
+            }
+        }
+    }
+    // the handle sees the table only once it is uploaded and the parameters are filled (d_id_tab marks "prepared")
+    double* d_tab = nullptr;
+    CFX_HIP(h, hipMalloc((void**)&d_tab, tab.size() * sizeof(double)));
+    const hipError_t up = hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (up != hipSuccess) {
+        (void)hipFree(d_tab);
+        return fail(h, CFX_EHIP, std::string("cfx_id: table upload: ") + hipGetErrorString(up));
+    }
+    IdParams P{};
+    P.B = p.batch;
+    P.N = N;
+    P.m = m;
+    P.T = T;
+    P.Q = Q;
+    P.dt = dt;
+    P.h = hh;
+    P.inv_tauc = 1.0 / c.tauc;
+    P.mult = c.fl * c.fv + c.fp;
+    P.r0_km = c.r0_km_relationship;
+    for (int s = 0; s < ID_SLOTS; ++s) P.def[s] = 0.0;
+    P.def[ID_A] = is_pw(h->model) ? c.a_scale : c.a_rest;
+    P.def[ID_KM] = c.km_rest;
+    P.def[ID_TAU1] = c.tau1_rest;
+    P.def[ID_TAU2] = c.tau2;
+    if (is_pw(h->model)) {
+        P.def[ID_P4] = c.pd0;
+        P.def[ID_P5] = c.pdt;
+    }
+    if (hmed) {
+        P.def[ID_P4] = c.ar;
+        P.def[ID_P5] = c.bs;
+        P.def[ID_P6] = c.Is;
+        P.def[ID_P7] = c.cr;
+    }
+    P.c0 = d_tab;
+    P.c1 = hmed ? nullptr : d_tab + nq;
+    P.w0 = hmed ? d_tab + nq : nullptr;
+    P.w1 = hmed ? d_tab + nq + nt : nullptr;
+    h->idp = P;
+    h->d_id_tab = d_tab;
+    return CFX_OK;
+}
+
+// Everything both identification calls check before they touch the device.
+static int id_validate(cfx_handle* h, const char* fn, int32_t n_id, const int32_t* ids, const double* theta,
+                       const double* u, int64_t n_data, int32_t* col) {
+    const std::string f(fn);
+    if (h->msk) return fail(h, CFX_EUNSUPPORTED, f + ": not available for a musculoskeletal handle");
+    if (h->colloc) return fail(h, CFX_EUNSUPPORTED, f + ": not available for a collocation transcription");
+    if (h->kp.tiled) return fail(h, CFX_EUNSUPPORTED, f + ": not available with CFX_LAYOUT_TILED64");
+    if (h->scheme != CFX_RK1 && h->scheme != CFX_RK2 && h->scheme != CFX_RK4)
+        return fail(h, CFX_EUNSUPPORTED, f + ": the scheme must be CFX_RK1, CFX_RK2 or CFX_RK4");
+    std::string msg;
+    const int rc = id_check(h->model, n_id, ids, col, msg);
+    if (rc != CFX_OK) return fail(h, rc, f + msg.substr(6));  // "cfx_id" -> the caller's name
+    if (!theta) return fail(h, CFX_EINVAL, f + ": theta is NULL");
+    if (h->sz.nu > 0 && !u) return fail(h, CFX_EINVAL, f + ": this model needs the controls u");
+    if (n_data != 1 && n_data != h->prob.batch)
+        return fail(h, CFX_EINVAL, f + ": n_data must be 1 or the batch size");
+    return CFX_OK;
+}
+
+static const double* id_in(cfx_handle* h, int slot, const double* p, size_t n, uint32_t flags, int* rc) {
+    if (flags & CFX_DEVICE) return p;
+    double* d = ensure(h, h->idbuf[slot], n, rc);
+    if (!d) return nullptr;
+    if (hipMemcpyAsync(d, p, n * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+        *rc = CFX_EHIP;
+        h->err = "hipMemcpyAsync H2D failed";
+        return nullptr;
+    }
+    return d;
+}
+
+static double* id_out(cfx_handle* h, int slot, double* p, size_t n, uint32_t flags, int* rc) {
+    return (flags & CFX_DEVICE) ? p : ensure(h, h->idbuf[slot], n, rc);
+}
+
+static int id_back(cfx_handle* h, const double* d, double* p, size_t n, uint32_t flags) {
+    if (flags & CFX_DEVICE) return CFX_OK;
+    CFX_HIP(h, hipMemcpyAsync(p, d, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return CFX_OK;
+}
+
+// slots 0..3 only: the 4-direction kernels
+static int id_dirs(const int32_t* col) {
+    for (int s = 4; s < ID_SLOTS; ++s)
+        if (col[s] >= 0) return 8;
+    return 4;
+}
+
+extern "C" int cfx_id_forces(cfx_handle* h, int32_t n_id, const int32_t* param_ids, const double* theta,
+                             const double* u, int64_t n_data, double* force, double* sens, uint32_t flags) {
+    if (!h) {
+        g_create_error = "cfx_id_forces: NULL handle";
+        return CFX_EINVAL;
+    }
+    int32_t col[ID_SLOTS];
+    int rc = id_validate(h, "cfx_id_forces", n_id, param_ids, theta, u, n_data, col);
+    if (rc != CFX_OK) return rc;
+    if (!force) return fail(h, CFX_EINVAL, "cfx_id_forces: force is NULL");
+    CFX_HIP(h, hipSetDevice(h->device));
+    if ((rc = id_prepare(h)) != CFX_OK) return rc;
+    IdParams P = h->idp;
+    P.n_data = n_data;
+    P.n_id = n_id;
+    for (int s = 0; s < ID_SLOTS; ++s) P.col[s] = col[s];
+    const size_t B = (size_t)P.B, nn = (size_t)P.N + 1, nu = (size_t)h->sz.nu;
+    const double* TH = id_in(h, 0, theta, (size_t)n_id * B, flags, &rc);
+    if (!TH) return rc;
+    const double* U = nu ? id_in(h, 1, u, (size_t)P.N * nu * (size_t)n_data, flags, &rc) : nullptr;
+    if (nu && !U) return rc;
+    double* F = id_out(h, 4, force, nn * B, flags, &rc);
+    if (!F) return rc;
+    double* S = sens ? id_out(h, 5, sens, nn * (size_t)n_id * B, flags, &rc) : nullptr;
+    if (sens && !S) return rc;
+    CFX_HIP(h, launch_id_sens(h->model, h->scheme, id_dirs(col), P, TH, U, F, S, h->stream));
+    if ((rc = id_back(h, F, force, nn * B, flags)) != CFX_OK) return rc;
+    if (sens && (rc = id_back(h, S, sens, nn * (size_t)n_id * B, flags)) != CFX_OK) return rc;
+    return sync_if_host(h, flags);
+}
+
+extern "C" int cfx_id_normal(cfx_handle* h, int32_t n_id, const int32_t* param_ids, const double* theta,
+                             const double* u, const double* target, const double* weight, int64_t n_data,
+                             double* cost, double* grad, double* gn, uint32_t flags) {
+    if (!h) {
+        g_create_error = "cfx_id_normal: NULL handle";
+        return CFX_EINVAL;
+    }
+    int32_t col[ID_SLOTS];
+    int rc = id_validate(h, "cfx_id_normal", n_id, param_ids, theta, u, n_data, col);
+    if (rc != CFX_OK) return rc;
+    if (!target || !weight) return fail(h, CFX_EINVAL, "cfx_id_normal: target or weight is NULL");
+    if (!cost || !grad || !gn) return fail(h, CFX_EINVAL, "cfx_id_normal: cost, grad or gn is NULL");
+    CFX_HIP(h, hipSetDevice(h->device));
+    if ((rc = id_prepare(h)) != CFX_OK) return rc;
+    IdParams P = h->idp;
+    P.n_data = n_data;
+    P.n_id = n_id;
+    for (int s = 0; s < ID_SLOTS; ++s) P.col[s] = col[s];
+    const size_t B = (size_t)P.B, nn = (size_t)P.N + 1, nu = (size_t)h->sz.nu, nd = (size_t)n_data;
+    const size_t npk = (size_t)n_id * (n_id + 1) / 2;
+    const double* TH = id_in(h, 0, theta, (size_t)n_id * B, flags, &rc);
+    if (!TH) return rc;
+    const double* U = nu ? id_in(h, 1, u, (size_t)P.N * nu * nd, flags, &rc) : nullptr;
+    if (nu && !U) return rc;
+    const double* Y = id_in(h, 2, target, nn * nd, flags, &rc);
+    if (!Y) return rc;
+    const double* W = id_in(h, 3, weight, nn * nd, flags, &rc);
+    if (!W) return rc;
+    double* C = id_out(h, 6, cost, B, flags, &rc);
+    if (!C) return rc;
+    double* G = id_out(h, 7, grad, (size_t)n_id * B, flags, &rc);
+    if (!G) return rc;
+    double* H = id_out(h, 8, gn, npk * B, flags, &rc);
+    if (!H) return rc;
+    CFX_HIP(h, launch_id_normal(h->model, h->scheme, id_dirs(col), P, TH, U, Y, W, C, G, H, h->stream));
+    if ((rc = id_back(h, C, cost, B, flags)) != CFX_OK) return rc;
+    if ((rc = id_back(h, G, grad, (size_t)n_id * B, flags)) != CFX_OK) return rc;
+    if ((rc = id_back(h, H, gn, npk * B, flags)) != CFX_OK) return rc;
     return sync_if_host(h, flags);
 }
 

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define CFX_ABI_VERSION 11
+#define CFX_ABI_VERSION 12
 
 /* return codes */
 #define CFX_OK 0
@@ -207,6 +207,43 @@ int cfx_eval_all_h(cfx_handle *h, const double *v, const double *obj_factor, con
 /* ---- IvpFes.integrate: single shooting from x0 (NULL: rest state) with per-interval controls
    u [N*nu per instance], writing every sub-step state: traj [(N*n_steps+1)*nx per instance]. ---- */
 int cfx_integrate(cfx_handle *h, const double *x0, const double *u, double *traj, uint32_t flags);
+
+/* ---- force-parameter identification (the reference's *_force_parameter_identification workflows) ----
+   Single shooting from the rest state of Ding2003, Ding2007 or Hmed2018 (no fatigue; RK1 / RK2 / RK4) with
+   PER-INSTANCE model constants: n_id (1..8) identified parameters, param_ids [n_id] (host array, CFX_P_*, distinct,
+   valid for the handle's model), theta [n_id][B].  Every other constant is the handle's.  Works on a handle from
+   cfx_create; fatigue models, collocation, CFX_LAYOUT_TILED64 and musculoskeletal handles: CFX_EUNSUPPORTED.
+   Every buffer of these two calls is SoA (element-major, instance-minor) whatever the handle's layout; host
+   pointers, or device pointers with CFX_DEVICE.
+   Experiment data come with a count n_data: 1 = one experiment shared by every instance (multistart), B = one per
+   instance (many subjects): u [N*nu][n_data] (Ding2007: the pulse width of every interval; Hmed2018: the T
+   intensities of every interval's window; Ding2003: ignored, may be NULL), target and weight [N+1][n_data].
+   cfx_id_forces: force [N+1][B], the node forces, and (sens != NULL) sens [N+1][n_id][B] = dF_k / dtheta_j.
+   cfx_id_normal: the normal equations of the weighted least-squares fit, with dt = final_time / N:
+     cost [B] = dt sum_k w_k (F_k - y_k)^2,  grad [n_id][B] = 2 dt sum_k w_k (F_k - y_k) S_kj,
+     gn [n_id (n_id + 1) / 2][B] = 2 dt sum_k w_k S_ki S_kj (packed lower triangle, i >= j at i (i + 1) / 2 + j).
+   cfx_id_check: the parameter-list checks of both calls for a model id, without a handle or a device (message
+   through cfx_last_error(NULL)). */
+enum {
+    CFX_P_A_REST = 0,
+    CFX_P_KM_REST = 1,
+    CFX_P_TAU1_REST = 2,
+    CFX_P_TAU2 = 3,
+    CFX_P_A_SCALE = 4,
+    CFX_P_PD0 = 5,
+    CFX_P_PDT = 6,
+    CFX_P_AR = 7,
+    CFX_P_BS = 8,
+    CFX_P_IS = 9,
+    CFX_P_CR = 10
+};
+#define CFX_ID_MAX_PARAMS 8
+int cfx_id_check(int32_t model, int32_t n_id, const int32_t *param_ids);
+int cfx_id_forces(cfx_handle *h, int32_t n_id, const int32_t *param_ids, const double *theta, const double *u,
+                  int64_t n_data, double *force, double *sens /* may be NULL */, uint32_t flags);
+int cfx_id_normal(cfx_handle *h, int32_t n_id, const int32_t *param_ids, const double *theta, const double *u,
+                  const double *target, const double *weight, int64_t n_data, double *cost, double *grad, double *gn,
+                  uint32_t flags);
 
 /* ---- musculoskeletal problems (FesMskModel + OcpFesMsk) --------------------------------------------
    Replaces the bioptim dynamics plugin FesMskModel registers (cocofest/models/dynamical_model.py:133-203,
