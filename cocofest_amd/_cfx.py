@@ -195,6 +195,8 @@ SIGNATURES = {
     "cfx_eval_all": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32]),
     "cfx_eval_all_h": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint32]),
     "cfx_integrate": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
+    "cfx_integrate_status": (C.c_int, [_P, _P, C.c_uint32]),
+    "cfx_collocation_points": (C.c_int, [_P, _D]),
     "cfx_id_check": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "cfx_id_forces": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, C.c_int64, _P, _P, C.c_uint32]),
     "cfx_id_normal": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, _P, C.c_int64, _P, _P, _P,
@@ -344,6 +346,8 @@ class Handle:
     contiguous) are used in place and the call is enqueued on torch's current stream.
     """
 
+    scheme = None  # the transcription (RK1 / RK2 / RK4 / COLLOCATION_*), set by _attach for every constructor
+
     def __init__(self, *, model_id, constants: dict, scheme, n_steps, n_shooting, truncation, final_time,
                  stim_rows, batch, layout=LAYOUT_SOA, n_params=0, last_stim_idx=None, intensity_floor=0.0,
                  objectives=(), device=0):
@@ -378,9 +382,9 @@ class Handle:
         pb.device = device
         h = C.c_void_p()
         rc = self.lib.cfx_create(C.byref(pb), C.byref(h))
-        self._attach(rc, h, batch, layout, n_shooting, n_steps, device)
+        self._attach(rc, h, batch, layout, n_shooting, n_steps, device, scheme)
 
-    def _attach(self, rc, h, batch, layout, n_shooting, n_steps, device):
+    def _attach(self, rc, h, batch, layout, n_shooting, n_steps, device, scheme):
         if rc != OK:
             raise CfxError(rc, self.lib.cfx_last_error(None).decode())
         self.h = h
@@ -389,7 +393,7 @@ class Handle:
         self.nv, self.ng, self.nnz_jac, self.nnz_hess = sz.nv, sz.ng, sz.nnz_jac, sz.nnz_hess
         self.nx, self.nu = sz.nx, sz.nu
         self.batch, self.layout, self.n_shooting, self.n_steps = batch, layout, n_shooting, n_steps
-        self.device = device
+        self.device, self.scheme = device, scheme
 
     def _check(self, rc):
         if rc != OK:
@@ -550,14 +554,54 @@ class Handle:
                                             _ptr(f), _ptr(grad), _ptr(hess), fl))
         return g, jac, hess
 
+    @property
+    def collocation(self) -> bool:
+        """True for a direct-collocation transcription (``n_steps`` is then the polynomial degree)."""
+        return self.scheme in (COLLOCATION_LEGENDRE, COLLOCATION_RADAU)
+
+    def collocation_points(self):
+        """tau_0 = 0 and the handle's d collocation points on (0, 1] (cfx_collocation_points)."""
+        tau = np.empty(self.n_steps + 1)
+        self._check(self.lib.cfx_collocation_points(self.h, tau.ctypes.data_as(_D)))
+        return tau
+
+    @property
+    def n_samples(self) -> int:
+        """Samples per instance of an ``integrate`` trajectory: every RK sub-step, or every interval's node state
+        and collocation states, then the final state."""
+        per = self.n_steps + 1 if self.collocation else self.n_steps
+        return self.n_shooting * per + 1
+
     def integrate(self, x0=None, u=None, traj=None):
-        n = (self.n_shooting * self.n_steps + 1) * self.nx
+        """Single shooting from ``x0`` (None: rest).  RK: every sub-step.  Collocation: the implicit integrator —
+        per interval x_k^0, x_k^1..x_k^d, then x_N; check ``integrate_status`` for convergence."""
+        n = self.n_samples * self.nx
         traj = np.empty(self._shape(n)) if traj is None else traj
         (x0, u, traj), fl = self._buffers(("x0", x0, self.nx, False), ("u", u, self.n_shooting * self.nu, False),
                                           ("traj", traj, n, True))
         self._torch_stream(fl)
         self._check(self.lib.cfx_integrate(self.h, _ptr(x0), _ptr(u), _ptr(traj), fl))
         return traj
+
+    def integrate_status(self, status=None):
+        """Per-instance int32 status of the last ``integrate`` (cfx_integrate_status): >= 0 the largest Newton
+        iteration count of any interval (0 for RK and for the models without fatigue), -(k+1) if interval k failed
+        to converge.  ``status``: None (a new host array), an int32 numpy array or an int32 CUDA tensor of batch."""
+        if status is None:
+            status = np.empty(self.batch, dtype=np.int32)
+        fl = 0
+        if _is_tensor(status):
+            if not status.is_cuda or status.device.index != self.device:
+                raise CfxError(EINVAL, f"status: device buffers must live on cuda:{self.device}")
+            if str(status.dtype) != "torch.int32" or not status.is_contiguous() or status.numel() != self.batch:
+                raise CfxError(EINVAL, "status: device buffers must be contiguous int32 tensors of batch elements")
+            fl = DEVICE
+        elif not (isinstance(status, np.ndarray) and status.dtype == np.int32 and status.flags.c_contiguous
+                  and status.size == self.batch):
+            raise CfxError(EINVAL, "status: host buffers must be C-contiguous int32 numpy arrays of batch elements")
+        self._torch_stream(fl)
+        self._check(self.lib.cfx_integrate_status(self.h, _ptr(status), fl))
+        return status
 
     # ---- force-parameter identification (always SoA buffers: (rows, instances)) ----
     def _id_buffers(self, slots):
@@ -688,7 +732,7 @@ class MskHandle(Handle):
             pb.n_marker_pairs, pb.marker_pairs = len(marker_pairs), mk
         h = C.c_void_p()
         rc = self.lib.cfx_msk_create(C.byref(pb), C.byref(h))
-        self._attach(rc, h, batch, layout, n_shooting, n_steps, device)
+        self._attach(rc, h, batch, layout, n_shooting, n_steps, device, scheme)
 
 
 class Ipm:

@@ -12,6 +12,7 @@
 #include "../../include/cfx.h"
 #include "cfx_aux.h"
 #include "cfx_colloc.h"
+#include "cfx_colloc_ivp.h"
 #include "cfx_ident.h"
 #include "cfx_internal.h"
 #include "cfx_launch.h"
@@ -42,6 +43,11 @@ struct cfx_handle {
     int model = 0, scheme = 1, tmax = 1, stages = 1, ni = 1, ni_g = 1;
     bool colloc = false;  // direct collocation (n_steps = polynomial degree)
     double tau[kMaxDeg + 1] = {};
+    // implicit collocation integrator (cfx_colloc_ivp.h): constant inverses built at the first cfx_integrate, the
+    // per-instance status of the last one; `integrated`: cfx_integrate has run on this handle (any transcription)
+    double* d_civp = nullptr;
+    int32_t* d_ivp_status = nullptr;
+    bool integrated = false;
     int32_t* d_hdiag = nullptr;
     KParams kp{};
     int device = 0;
@@ -811,7 +817,7 @@ extern "C" void cfx_destroy(cfx_handle* h) {
     for (void* p : {(void*)h->d_tab, (void*)h->d_rest, (void*)h->d_cna, (void*)h->d_htasks, (void*)h->d_obj,
                     (void*)h->d_targets, (void*)h->d_sl_param, (void*)h->d_sl_joff, (void*)h->d_hdiag,
                     (void*)h->d_geom, (void*)h->d_mobj, (void*)h->d_msk_imin, (void*)h->d_mk, (void*)h->d_ties,
-                    (void*)h->d_cs1, (void*)h->d_id_tab})
+                    (void*)h->d_cs1, (void*)h->d_id_tab, (void*)h->d_civp, (void*)h->d_ivp_status})
         if (p) (void)hipFree(p);
     for (DevBuf& b : h->idbuf)
         if (b.p) (void)hipFree(b.p);
@@ -1071,12 +1077,110 @@ extern "C" int cfx_eval_all_h(cfx_handle* h, const double* v, const double* obj_
     return sync_if_host(h, flags);
 }
 
+// Inverse of the d x d matrix a (row-major, overwritten) by Gauss-Jordan elimination with partial pivoting, in
+// long double; false when a pivot vanishes.
+static bool invert_small(int d, std::vector<long double>& a, std::vector<long double>& inv) {
+    inv.assign((size_t)d * d, 0.0L);
+    for (int i = 0; i < d; ++i) inv[(size_t)i * d + i] = 1.0L;
+    for (int c = 0; c < d; ++c) {
+        int p = c;
+        for (int r = c + 1; r < d; ++r)
+            if (std::fabs(a[(size_t)r * d + c]) > std::fabs(a[(size_t)p * d + c])) p = r;
+        if (a[(size_t)p * d + c] == 0.0L) return false;
+        for (int cc = 0; cc < d; ++cc) {
+            std::swap(a[(size_t)c * d + cc], a[(size_t)p * d + cc]);
+            std::swap(inv[(size_t)c * d + cc], inv[(size_t)p * d + cc]);
+        }
+        const long double piv = a[(size_t)c * d + c];
+        for (int cc = 0; cc < d; ++cc) {
+            a[(size_t)c * d + cc] /= piv;
+            inv[(size_t)c * d + cc] /= piv;
+        }
+        for (int r = 0; r < d; ++r) {
+            if (r == c) continue;
+            const long double m = a[(size_t)r * d + c];
+            for (int cc = 0; cc < d; ++cc) {
+                a[(size_t)r * d + cc] -= m * a[(size_t)c * d + cc];
+                inv[(size_t)r * d + cc] -= m * inv[(size_t)c * d + cc];
+            }
+        }
+    }
+    return true;
+}
+
+// The constant maps of the implicit collocation integrator (cfx_colloc_ivp.h), from the handle's own C[i][j]:
+// with Chat[j][i] = C[i][j] (i, j >= 1), c0[j] = C[0][j] and M(kappa) = (Chat + kappa I)^-1,
+//   McS = (dt / tauc) M(dt / tauc),  vc0 = -M(dt / tauc) c0                        (calcium)
+//   MfD = dt M(dt / tau_fat),  vf0 = -M(dt / tau_fat) c0,  wf = (dt / tau_fat) M(dt / tau_fat) 1   (fatigue states)
+static bool civp_tables(const cfx_handle* h, std::vector<double>& tb) {
+    const KParams& kp = h->kp;
+    const int d = kp.deg;
+    tb.assign((size_t)civp_table_len(d), 0.0);
+    auto build = [&](long double kappa, std::vector<long double>& inv) {
+        std::vector<long double> a((size_t)d * d);
+        for (int j = 0; j < d; ++j)
+            for (int i = 0; i < d; ++i) a[(size_t)j * d + i] = (long double)kp.colC[i + 1][j + 1] + (i == j ? kappa : 0.0L);
+        return invert_small(d, a, inv);
+    };
+    std::vector<long double> inv;
+    const long double kc = (long double)kp.dt * kp.inv_tauc;
+    if (!build(kc, inv)) return false;
+    for (int j = 0; j < d; ++j) {
+        long double v = 0.0L;
+        for (int i = 0; i < d; ++i) {
+            tb[(size_t)j * d + i] = (double)(kc * inv[(size_t)j * d + i]);
+            v -= inv[(size_t)j * d + i] * kp.colC[0][i + 1];
+        }
+        tb[(size_t)civp_off_vc0(d) + j] = (double)v;
+    }
+    if (is_fatigue(h->model)) {
+        const long double kf = (long double)kp.dt * kp.inv_tau_fat;
+        if (!build(kf, inv)) return false;
+        for (int j = 0; j < d; ++j) {
+            long double v = 0.0L, w = 0.0L;
+            for (int i = 0; i < d; ++i) {
+                tb[(size_t)civp_off_mf(d) + (size_t)j * d + i] = (double)((long double)kp.dt * inv[(size_t)j * d + i]);
+                v -= inv[(size_t)j * d + i] * kp.colC[0][i + 1];
+                w += kf * inv[(size_t)j * d + i];
+            }
+            tb[(size_t)civp_off_vf0(d) + j] = (double)v;
+            tb[(size_t)civp_off_wf(d) + j] = (double)w;
+        }
+    }
+    return true;
+}
+
+// cfx_integrate on a collocation handle: every interval's node state and collocation states, then x_N
+static int colloc_integrate(cfx_handle* h, const double* x0, const double* u, double* traj, uint32_t flags) {
+    h->integrated = false;  // a call that fails before its launch leaves no status to report
+    CFX_HIP(h, hipSetDevice(h->device));
+    if (!h->d_civp) {
+        std::vector<double> tb;
+        if (!civp_tables(h, tb)) return fail(h, CFX_EINVAL, "cfx_integrate: singular collocation matrix");
+        CFX_HIP(h, hipMalloc((void**)&h->d_civp, tb.size() * sizeof(double)));
+        CFX_HIP(h, hipMemcpy(h->d_civp, tb.data(), tb.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (!h->d_ivp_status) CFX_HIP(h, hipMalloc((void**)&h->d_ivp_status, (size_t)h->prob.batch * sizeof(int32_t)));
+    int rc = CFX_OK;
+    const int64_t nsamp = (int64_t)h->kp.N * (h->kp.deg + 1) + 1;
+    const double* X0 = x0 ? stage_in(h, S_A1, x0, h->sz.nx, flags, &rc) : nullptr;
+    if (x0 && !X0) return rc;
+    const double* U = h->sz.nu ? stage_in(h, S_A2, u, (int64_t)h->kp.N * h->sz.nu, flags, &rc) : nullptr;
+    if (h->sz.nu && !U) return rc;
+    double* TR = stage_out(h, S_OUT, traj, nsamp * h->sz.nx, flags, &rc);
+    if (!TR) return rc;
+    CFX_HIP(h, launch_colloc_ivp(h->model, h->tmax, h->kp, h->d_civp, X0, U, TR, h->d_ivp_status, h->stream));
+    h->integrated = true;
+    if ((rc = finish_out(h, S_OUT, TR, traj, nsamp * h->sz.nx, flags)) != CFX_OK) return rc;
+    return sync_if_host(h, flags);
+}
+
 extern "C" int cfx_integrate(cfx_handle* h, const double* x0, const double* u, double* traj, uint32_t flags) {
     if (!h || !traj) return CFX_EINVAL;
     if (h->msk) return msk_integrate(h, x0, u, traj, flags);
-    if (h->colloc) return fail(h, CFX_EUNSUPPORTED, "cfx_integrate: not available for a collocation transcription");
     if (h->kp.tiled) return fail(h, CFX_EUNSUPPORTED, "cfx_integrate: not available with CFX_LAYOUT_TILED64");
     if (h->sz.nu > 0 && !u) return fail(h, CFX_EINVAL, "cfx_integrate: this model needs per-interval controls");
+    if (h->colloc) return colloc_integrate(h, x0, u, traj, flags);
     CFX_HIP(h, hipSetDevice(h->device));
     int rc = CFX_OK;
     const int64_t nsamp = (int64_t)h->kp.N * h->kp.m + 1;
@@ -1089,8 +1193,36 @@ extern "C" int cfx_integrate(cfx_handle* h, const double* x0, const double* u, d
     hipError_t e = is_int(h->model) ? launch_ivp_hmed(h->model, h->scheme, h->tmax, h->kp, X0, U, TR, h->stream)
                                     : launch_ivp_ding(h->model, h->scheme, h->kp, X0, U, TR, h->stream);
     CFX_HIP(h, e);
+    h->integrated = true;
     if ((rc = finish_out(h, S_OUT, TR, traj, nsamp * h->sz.nx, flags)) != CFX_OK) return rc;
     return sync_if_host(h, flags);
+}
+
+extern "C" int cfx_integrate_status(cfx_handle* h, int32_t* status, uint32_t flags) {
+    if (!h) {
+        g_create_error = "cfx_integrate_status: handle is NULL";
+        return CFX_EINVAL;
+    }
+    if (!status) return fail(h, CFX_EINVAL, "cfx_integrate_status: status is NULL");
+    if (!h->integrated) return fail(h, CFX_EINVAL, "cfx_integrate_status: no cfx_integrate has run on this handle");
+    CFX_HIP(h, hipSetDevice(h->device));
+    const size_t bytes = (size_t)h->prob.batch * sizeof(int32_t);
+    const bool dev = flags & CFX_DEVICE;
+    if (h->colloc && !h->msk) {
+        CFX_HIP(h, hipMemcpyAsync(status, h->d_ivp_status, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                                  h->stream));
+    } else if (dev) {  // explicit Runge-Kutta: nothing is iterated
+        CFX_HIP(h, hipMemsetAsync(status, 0, bytes, h->stream));
+    } else {
+        std::memset(status, 0, bytes);
+    }
+    return sync_if_host(h, flags);
+}
+
+extern "C" int cfx_collocation_points(const cfx_handle* h, double* tau) {
+    if (!h || !tau || !h->colloc) return CFX_EINVAL;
+    std::memcpy(tau, h->tau, (size_t)(h->kp.deg + 1) * sizeof(double));
+    return CFX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1994,6 +2126,7 @@ static int msk_integrate(cfx_handle* h, const double* x0, const double* u, doubl
     double* TR = stage_out(h, S_OUT, traj, nsamp * h->sz.nx, flags, &rc);
     if (!TR) return rc;
     CFX_HIP(h, launch_msk_ivp(h->msk_nq, h->msk_nm, h->msk_fam, h->scheme, h->mp, h->d_geom, X0, U, TR, h->stream));
+    h->integrated = true;
     if ((rc = finish_out(h, S_OUT, TR, traj, nsamp * h->sz.nx, flags)) != CFX_OK) return rc;
     return sync_if_host(h, flags);
 }

@@ -65,6 +65,11 @@ hipError_t launch_colloc(int model, int tmax, int ni, const KParams& P, const do
 hipError_t launch_colloc_hess(int model, int tmax, const KParams& P, const HTask* tasks, int ntasks, int bs,
                               const double* V, const double* LAM, double* H, double* G, double* J, hipStream_t s);
 
+// implicit collocation integrator (cfx_colloc_ivp.h, instantiated in cfx_inst_colloc_ivp.hip): TB the host-built
+// tables of the handle's degree and step (civp_table_len doubles), ST the per-instance status [B]
+hipError_t launch_colloc_ivp(int model, int tmax, const KParams& P, const double* TB, const double* X0,
+                             const double* U, double* TR, int32_t* ST, hipStream_t s);
+
 template <int MODEL, int SCHEME, int DJ, int TMAX>
 hipError_t launch_hessian_t(const KParams& P, const HTask* tasks, int ntasks, int bs, const double* V,
                             const double* LAM, double* H, double* G, double* J, hipStream_t s) {

@@ -2,7 +2,9 @@
 
 Same constructor dictionaries, defaults, pulse modes and validation messages as the reference.  The
 integration itself (single shooting, every RK sub-step returned) runs on the GPU through
-``cfx_integrate``; batches of independent instances use :meth:`IvpFes.handle`.
+``cfx_integrate``; batches of independent instances use :meth:`IvpFes.handle`.  With
+``OdeSolver.COLLOCATION`` the same call runs the implicit collocation integrator: every interval's node
+state and collocation states are returned.
 """
 
 from __future__ import annotations
@@ -160,8 +162,6 @@ class IvpFes:
 
     # ---- integration ---------------------------------------------------------------------------------
     def handle(self, batch: int = 1, layout: str = "aos", device: int = 0) -> _cfx.Handle:
-        if isinstance(self.ode_solver, OdeSolver.COLLOCATION):
-            raise NotImplementedError("COLLOCATION integration is not available in libcfx yet")
         return _cfx.Handle(model_id=self.model.cfx_model_id, constants=self.model.cfx_constants(),
                            scheme=self.ode_solver.scheme, n_steps=self.ode_solver.n_integration_steps,
                            n_shooting=self.n_shooting, truncation=self.model._sum_stim_truncation,
@@ -170,15 +170,29 @@ class IvpFes:
 
     def integrate(self, shooting_type=None, integrator=None, to_merge=None, return_time=True,
                   duplicated_times=False):
-        """Single-shooting integration from the rest state; returns {state: (1, N*m+1)} (and the time)."""
+        """Single-shooting integration from the rest state; returns {state: (1, N*m+1)} (and the time).
+
+        ``OdeSolver.COLLOCATION`` (degree d): {state: (1, N*(d+1)+1)} — per interval the node state and the d
+        collocation states, then the final state — at the times t_k + tau_j dt (tau_0 = 0), then ``final_time``.
+        Raises ``RuntimeError`` if an interval's collocation equations did not converge."""
         if getattr(self, "_h1", None) is None:  # the handle (tables, buffers) is built once per IvpFes
             self._h1 = self.handle(batch=1)
             self._u1 = self.controls.T.reshape(1, -1).copy() if self.controls.shape[0] else None
         traj = self._h1.integrate(u=self._u1)
         m = self.ode_solver.n_integration_steps
         nx = self.model.nb_state
-        traj = traj.reshape(self.n_shooting * m + 1, nx)
+        traj = traj.reshape(self._h1.n_samples, nx)
         result = {name: traj[:, i][np.newaxis, :] for i, name in enumerate(self.model.name_dof)}
+        if self._h1.collocation:
+            status = int(self._h1.integrate_status()[0])
+            if status < 0:
+                raise RuntimeError(f"collocation integration did not converge in interval {-status - 1}")
+            if not return_time:
+                return result
+            dt = self.final_time / self.n_shooting
+            tau = self._h1.collocation_points()
+            time = np.array([k * dt + t * dt for k in range(self.n_shooting) for t in tau] + [float(self.final_time)])
+            return result, time
         if not return_time:
             return result
         hstep = self.final_time / self.n_shooting / m

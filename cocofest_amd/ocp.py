@@ -250,6 +250,39 @@ class FesOcp:
     def initial_guess_vector(self):
         return self.pack(self.x_init, self.u_init if self.nu else None, self.p_init)
 
+    def integrated_guess(self, batch: int = 1, device: int = 0):
+        """A dynamically feasible start, (batch, nv): controls ``u_init``, parameters ``p_init``, and the states
+        integrated on the GPU (``cfx_integrate``) from the node-0 initial state with this problem's own scheme.
+
+        Collocation problems take every node and point state from the implicit collocation integrator; RK problems
+        take every m-th sub-step of the single-shooting trajectory.  For Hmed problems with intensity parameters the
+        controls are the sliding windows of ``p_init``.  Every continuity, defect and sliding-window row of
+        ``eval_g`` is zero to rounding at this vector (``initial_guess_vector`` leaves them violated); pass it as
+        ``solve_ocp(..., v0=...)``.  Raises ``RuntimeError`` if the collocation equations did not converge."""
+        N, nx, nu, d = self.n_shooting, self.nx, self.nu, self.degree
+        u = np.asarray(self.u_init, dtype=float).reshape(nu, N).copy()
+        if self.n_params and self.last_stim_idx is not None:
+            p = np.asarray(self.p_init, dtype=float)
+            for k in range(N):
+                window = list(p[: int(self.last_stim_idx[k]) + 1][-nu:])
+                u[:, k] = [self.intensity_floor] * (nu - len(window)) + window
+        h = self.nlp(batch=1, device=device)
+        try:
+            traj = h.integrate(x0=np.asarray(self.x_init, dtype=float)[:, 0], u=u.T.reshape(1, -1) if nu else None)
+            status = int(h.integrate_status()[0])
+            samples = traj.reshape(h.n_samples, nx)
+        finally:
+            h.close()
+        if status < 0:
+            raise RuntimeError(f"collocation integration did not converge in interval {-status - 1}")
+        if d:
+            body = samples[:-1].reshape(N, d + 1, nx)
+            x = np.concatenate([body[:, 0, :], samples[-1:]], axis=0).T
+            v = self.pack(x, u if nu else None, self.p_init, x_points=body[:, 1:, :].transpose(2, 0, 1))
+        else:
+            v = self.pack(samples[:: self.ode_solver.n_integration_steps].T, u if nu else None, self.p_init)
+        return np.tile(v, (batch, 1))
+
     # ---- GPU callbacks ------------------------------------------------------------------------------
     def nlp(self, batch: int = 1, layout: str = "aos", device: int = 0) -> _cfx.Handle:
         """Open a libcfx handle evaluating ``batch`` instances of this problem on GPU ``device``."""

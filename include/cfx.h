@@ -67,7 +67,8 @@ extern "C" {
 /* direct collocation (OdeSolver.COLLOCATION(polynomial_degree, method)): one Lagrange polynomial per shooting
    interval through the node state and `n_steps` (= the degree d, 1..9) Legendre or Radau IIA points.
    Decision block per interval [x_k^0, x_k^1..x_k^d, u_k]; rows per interval: d defect blocks of nx, the
-   continuity block of nx, then the sliding-window rows.  cfx_integrate is not available for it. */
+   continuity block of nx, then the sliding-window rows.  cfx_integrate solves the same defect rows interval by
+   interval (an implicit integrator, see cfx_integrate). */
 #define CFX_COLLOCATION_LEGENDRE 16
 #define CFX_COLLOCATION_RADAU 17
 
@@ -205,8 +206,29 @@ int cfx_eval_all_h(cfx_handle *h, const double *v, const double *obj_factor, con
                    double *jac, double *f, double *grad, double *hess, uint32_t flags);
 
 /* ---- IvpFes.integrate: single shooting from x0 (NULL: rest state) with per-interval controls
-   u [N*nu per instance], writing every sub-step state: traj [(N*n_steps+1)*nx per instance]. ---- */
+   u [N*nu per instance], writing every sub-step state: traj [(N*n_steps+1)*nx per instance].
+   On a collocation handle (degree d = n_steps) every interval's defect equations are solved from its node state
+   and traj holds [(N*(d+1)+1)*nx per instance]: for each interval x_k^0, x_k^1..x_k^d, then x_N, the state part
+   of the collocation decision vector in its order (x_{k+1}^0 = sum_i D[i] x_k^i, also when tau_d = 1).  The
+   fatigue models iterate (Newton, at most 20 updates per interval); an instance whose interval does not converge
+   gets NaN from that interval's points on and a negative cfx_integrate_status, the call itself returns CFX_OK.
+   CFX_LAYOUT_TILED64: CFX_EUNSUPPORTED. ---- */
 int cfx_integrate(cfx_handle *h, const double *x0, const double *u, double *traj, uint32_t flags);
+/* status [B] (int32; host, or device with CFX_DEVICE) of the handle's last cfx_integrate: >= 0 the largest Newton
+   iteration count any interval of the instance took (0 for the linear collocation solves of the models without
+   fatigue and for every Runge-Kutta handle), -(k+1) when interval k was the first that failed to converge.
+   CFX_EINVAL (with a message) for a NULL handle or status, and before any cfx_integrate on the handle; a
+   collocation cfx_integrate that fails before its launch (staging, allocation) leaves no status either, so the
+   status of an earlier run is never reported for it.
+   A status >= 0 says that the iteration converged, not which solution it reached: the defect equations of the
+   fatigue models have further, non-physical solutions (negative Tau1 / Km), and the integrator does not test for
+   them.  It starts every interval from F^j = F^0 with the exact calcium and consistent fatigue states, which
+   reached the physical solution on every input tried; a caller who integrates far outside the models' range
+   should check the signs of Tau1 and Km in the trajectory. */
+int cfx_integrate_status(cfx_handle *h, int32_t *status, uint32_t flags);
+/* tau [d+1] (host): tau_0 = 0 and the handle's d collocation points on (0, 1], the ones its coefficients and
+   stimulation tables were built from.  CFX_EINVAL unless the handle is a collocation transcription. */
+int cfx_collocation_points(const cfx_handle *h, double *tau);
 
 /* ---- force-parameter identification (the reference's *_force_parameter_identification workflows) ----
    Single shooting from the rest state of Ding2003, Ding2007 or Hmed2018 (no fatigue; RK1 / RK2 / RK4) with
