@@ -20,7 +20,7 @@ from .fes_models import (
     ModelMaker,
 )
 from .fourier import FourierSeries
-from .identification import FesIdentification
+from .identification import FesFatigueIdentification, FesIdentification
 from .ivp import IvpFes
 from .msk import FesMskModel, FesMskOcp, OcpFesMsk
 from .nmpc import FesNmpc, NmpcFesMsk, NmpcResult
@@ -32,6 +32,6 @@ __all__ = [
     "CfxError", "Handle", "load_library", "DingModelFrequency", "DingModelFrequencyWithFatigue",
     "DingModelPulseIntensityFrequency", "DingModelPulseIntensityFrequencyWithFatigue",
     "DingModelPulseWidthFrequency", "DingModelPulseWidthFrequencyWithFatigue", "FesModel", "ModelMaker",
-    "FourierSeries", "FesIdentification", "IvpFes", "FesOcp", "Axis", "Constraint", "ConstraintFcn", "ConstraintList", "Node", "Objective", "ObjectiveFcn", "ObjectiveList", "OcpFes",
+    "FourierSeries", "FesIdentification", "FesFatigueIdentification", "IvpFes", "FesOcp", "Axis", "Constraint", "ConstraintFcn", "ConstraintList", "Node", "Objective", "ObjectiveFcn", "ObjectiveList", "OcpFes",
     "ControlType", "OdeSolver", "FesMskModel", "FesMskOcp", "OcpFesMsk", "FesNmpc", "NmpcFesMsk", "NmpcResult", "BatchedIpm", "IpmOptions", "IpmResult", "Solver",
 ]

@@ -38,6 +38,9 @@ VAR_STATE, VAR_CONTROL = 0, 1
 PARAM_IDS = {"a_rest": 0, "km_rest": 1, "tau1_rest": 2, "tau2": 3, "a_scale": 4, "pd0": 5, "pdt": 6, "ar": 7, "bs": 8,
              "Is": 9, "cr": 10}
 ID_MAX_PARAMS = 8
+# identified fatigue-parameter ids (CFX_FP_*) of the fatigue-parameter identification
+FATIGUE_PARAM_IDS = {"alpha_a": 0, "alpha_tau1": 1, "alpha_km": 2, "tau_fat": 3}
+IDF_MAX_PARAMS = 4
 
 
 class CfxError(RuntimeError):
@@ -201,6 +204,10 @@ SIGNATURES = {
     "cfx_id_forces": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, C.c_int64, _P, _P, C.c_uint32]),
     "cfx_id_normal": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, _P, C.c_int64, _P, _P, _P,
                                 C.c_uint32]),
+    "cfx_idf_check": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "cfx_idf_forces": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, C.c_int64, _P, _P, C.c_uint32]),
+    "cfx_idf_normal": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, _P, C.c_int64, _P, _P, _P,
+                                 C.c_uint32]),
     "cfx_msk_create": (C.c_int, [C.POINTER(MskProblem), C.POINTER(_P)]),
     "cfx_band_lu": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32, _P, _P]),
     "cfx_band_lu_solve": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, _P, _P, C.c_int32, _P, _P]),
@@ -618,6 +625,14 @@ class Handle:
     def id_forces(self, param_ids, theta, u=None, n_data=1, force=None, sens=None, with_sens=False):
         """cfx_id_forces: node forces (N+1, B) and, with ``with_sens`` or a ``sens`` buffer, dF_k / dtheta_j
         (N+1, n_id, B) for per-instance parameters theta (n_id, B).  Returns (force, sens or None)."""
+        return self._id_forces(self.lib.cfx_id_forces, param_ids, theta, u, n_data, force, sens, with_sens)
+
+    def idf_forces(self, param_ids, theta, u=None, n_data=1, force=None, sens=None, with_sens=False):
+        """cfx_idf_forces: as ``id_forces`` for per-instance FATIGUE parameters (``FATIGUE_PARAM_IDS``) of a fatigue
+        model, from the fatigue rest state."""
+        return self._id_forces(self.lib.cfx_idf_forces, param_ids, theta, u, n_data, force, sens, with_sens)
+
+    def _id_forces(self, call, param_ids, theta, u, n_data, force, sens, with_sens):
         ids, idp, n_id = self._id_args(param_ids, n_data)
         N, B = self.n_shooting, self.batch
         if _is_tensor(theta):
@@ -633,13 +648,20 @@ class Handle:
             ("theta", theta, n_id * B, False), ("u", u if self.nu else None, N * self.nu * n_data, False),
             ("force", force, (N + 1) * B, True), ("sens", sens, (N + 1) * n_id * B, True)])
         self._torch_stream(fl)
-        self._check(self.lib.cfx_id_forces(self.h, n_id, idp, _ptr(theta), _ptr(u), n_data, _ptr(force), _ptr(sens),
-                                           fl))
+        self._check(call(self.h, n_id, idp, _ptr(theta), _ptr(u), n_data, _ptr(force), _ptr(sens), fl))
         return force, sens
 
     def id_normal(self, param_ids, theta, target, weight, u=None, n_data=1, cost=None, grad=None, gn=None):
         """cfx_id_normal: cost (B,), grad (n_id, B) and the packed lower triangle of the Gauss-Newton matrix
         (n_id (n_id + 1) / 2, B) of the weighted least-squares fit to target / weight (N+1, n_data)."""
+        return self._id_normal(self.lib.cfx_id_normal, param_ids, theta, target, weight, u, n_data, cost, grad, gn)
+
+    def idf_normal(self, param_ids, theta, target, weight, u=None, n_data=1, cost=None, grad=None, gn=None):
+        """cfx_idf_normal: as ``id_normal`` for per-instance FATIGUE parameters (``FATIGUE_PARAM_IDS``) of a fatigue
+        model."""
+        return self._id_normal(self.lib.cfx_idf_normal, param_ids, theta, target, weight, u, n_data, cost, grad, gn)
+
+    def _id_normal(self, call, param_ids, theta, target, weight, u, n_data, cost, grad, gn):
         ids, idp, n_id = self._id_args(param_ids, n_data)
         N, B = self.n_shooting, self.batch
         npk = n_id * (n_id + 1) // 2
@@ -657,8 +679,8 @@ class Handle:
             ("target", target, (N + 1) * n_data, False), ("weight", weight, (N + 1) * n_data, False),
             ("cost", cost, B, True), ("grad", grad, n_id * B, True), ("gn", gn, npk * B, True)])
         self._torch_stream(fl)
-        self._check(self.lib.cfx_id_normal(self.h, n_id, idp, _ptr(theta), _ptr(u), _ptr(target), _ptr(weight),
-                                           n_data, _ptr(cost), _ptr(grad), _ptr(gn), fl))
+        self._check(call(self.h, n_id, idp, _ptr(theta), _ptr(u), _ptr(target), _ptr(weight), n_data, _ptr(cost),
+                         _ptr(grad), _ptr(gn), fl))
         return cost, grad, gn
 
     def synchronize(self):

@@ -14,6 +14,7 @@
 #include "cfx_colloc.h"
 #include "cfx_colloc_ivp.h"
 #include "cfx_ident.h"
+#include "cfx_identf.h"
 #include "cfx_internal.h"
 #include "cfx_launch.h"
 #include "cfx_msk_launch.h"
@@ -1493,6 +1494,175 @@ extern "C" int cfx_id_normal(cfx_handle* h, int32_t n_id, const int32_t* param_i
     double* H = id_out(h, 8, gn, npk * B, flags, &rc);
     if (!H) return rc;
     CFX_HIP(h, launch_id_normal(h->model, h->scheme, id_dirs(col), P, TH, U, Y, W, C, G, H, h->stream));
+    if ((rc = id_back(h, C, cost, B, flags)) != CFX_OK) return rc;
+    if ((rc = id_back(h, G, grad, (size_t)n_id * B, flags)) != CFX_OK) return rc;
+    if ((rc = id_back(h, H, gn, npk * B, flags)) != CFX_OK) return rc;
+    return sync_if_host(h, flags);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// fatigue-parameter identification (cfx_identf.h)
+// ------------------------------------------------------------------------------------------------------
+// The parameter-list checks; col[slot] = column of the slot in theta (-1: not identified).  The CFX_FP_* ids are
+// the direction slots.
+static int idf_check(int model, int32_t n_id, const int32_t* ids, int32_t* col, std::string& msg) {
+    if (model < CFX_DING2003 || model > CFX_HMED2018_FATIGUE) {
+        msg = "cfx_idf: unknown model";
+        return CFX_EINVAL;
+    }
+    if (!is_fatigue(model)) {
+        msg = "cfx_idf: fatigue-parameter identification is only available for the fatigue models";
+        return CFX_EUNSUPPORTED;
+    }
+    if (n_id < 1 || n_id > CFX_IDF_MAX_PARAMS) {
+        msg = "cfx_idf: n_id must be in [1, 4]";
+        return CFX_EINVAL;
+    }
+    if (!ids) {
+        msg = "cfx_idf: param_ids is NULL";
+        return CFX_EINVAL;
+    }
+    for (int s = 0; s < IDF_SLOTS; ++s) col[s] = -1;
+    for (int j = 0; j < n_id; ++j) {
+        if (ids[j] < CFX_FP_ALPHA_A || ids[j] > CFX_FP_TAU_FAT) {
+            msg = "cfx_idf: unknown parameter id " + std::to_string(ids[j]);
+            return CFX_EINVAL;
+        }
+        if (col[ids[j]] >= 0) {
+            msg = "cfx_idf: duplicate parameter id " + std::to_string(ids[j]);
+            return CFX_EINVAL;
+        }
+        col[ids[j]] = j;
+    }
+    return CFX_OK;
+}
+
+extern "C" int cfx_idf_check(int32_t model, int32_t n_id, const int32_t* param_ids) {
+    int32_t col[IDF_SLOTS];
+    return idf_check(model, n_id, param_ids, col, g_create_error);
+}
+
+// Everything both calls check before they touch the device (the order and the messages of id_validate).
+static int idf_validate(cfx_handle* h, const char* fn, int32_t n_id, const int32_t* ids, const double* theta,
+                        const double* u, int64_t n_data, int32_t* col) {
+    const std::string f(fn);
+    if (h->msk) return fail(h, CFX_EUNSUPPORTED, f + ": not available for a musculoskeletal handle");
+    if (h->colloc) return fail(h, CFX_EUNSUPPORTED, f + ": not available for a collocation transcription");
+    if (h->kp.tiled) return fail(h, CFX_EUNSUPPORTED, f + ": not available with CFX_LAYOUT_TILED64");
+    if (h->scheme != CFX_RK1 && h->scheme != CFX_RK2 && h->scheme != CFX_RK4)
+        return fail(h, CFX_EUNSUPPORTED, f + ": the scheme must be CFX_RK1, CFX_RK2 or CFX_RK4");
+    std::string msg;
+    const int rc = idf_check(h->model, n_id, ids, col, msg);
+    if (rc != CFX_OK) return fail(h, rc, f + msg.substr(7));  // "cfx_idf" -> the caller's name
+    if (!theta) return fail(h, CFX_EINVAL, f + ": theta is NULL");
+    if (h->sz.nu > 0 && !u) return fail(h, CFX_EINVAL, f + ": this model needs the controls u");
+    if (n_data != 1 && n_data != h->prob.batch)
+        return fail(h, CFX_EINVAL, f + ": n_data must be 1 or the batch size");
+    return CFX_OK;
+}
+
+// Kernel parameters of one call.  The stimulation tables are those of the force-parameter identification
+// (id_prepare): they depend on the stimulation rows alone, and a fatigue handle has no other use for them.
+static int idf_params(cfx_handle* h, int32_t n_id, const int32_t* col, int64_t n_data, IdfParams& P) {
+    const int rc = id_prepare(h);
+    if (rc != CFX_OK) return rc;
+    const IdParams& I = h->idp;
+    const cfx_constants& c = h->prob.constants;
+    P = IdfParams{};
+    P.B = I.B;
+    P.n_data = n_data;
+    P.N = I.N;
+    P.m = I.m;
+    P.T = I.T;
+    P.Q = I.Q;
+    P.n_id = n_id;
+    for (int s = 0; s < IDF_SLOTS; ++s) P.col[s] = col[s];
+    P.def[IDF_AA] = c.alpha_a;
+    P.def[IDF_AT] = c.alpha_tau1;
+    P.def[IDF_AK] = c.alpha_km;
+    P.def[IDF_TF] = c.tau_fat;
+    P.dt = I.dt;
+    P.h = I.h;
+    P.inv_tauc = I.inv_tauc;
+    P.mult = I.mult;
+    P.r0m1 = c.km_rest + c.r0_km_relationship - 1.0;
+    P.a_rest = is_pw(h->model) ? c.a_scale : c.a_rest;  // ding2007_with_fatigue.py:198-241: A relaxes to a_scale
+    P.tau1_rest = c.tau1_rest;
+    P.km_rest = c.km_rest;
+    P.tau2 = c.tau2;
+    P.pd0 = c.pd0;
+    P.pdt = c.pdt;
+    P.ar = c.ar;
+    P.bs = c.bs;
+    P.Is = c.Is;
+    P.cr = c.cr;
+    P.c0 = I.c0;
+    P.c1 = I.c1;
+    P.w0 = I.w0;
+    P.w1 = I.w1;
+    return CFX_OK;
+}
+
+extern "C" int cfx_idf_forces(cfx_handle* h, int32_t n_id, const int32_t* param_ids, const double* theta,
+                              const double* u, int64_t n_data, double* force, double* sens, uint32_t flags) {
+    if (!h) {
+        g_create_error = "cfx_idf_forces: NULL handle";
+        return CFX_EINVAL;
+    }
+    int32_t col[IDF_SLOTS];
+    int rc = idf_validate(h, "cfx_idf_forces", n_id, param_ids, theta, u, n_data, col);
+    if (rc != CFX_OK) return rc;
+    if (!force) return fail(h, CFX_EINVAL, "cfx_idf_forces: force is NULL");
+    CFX_HIP(h, hipSetDevice(h->device));
+    IdfParams P;
+    if ((rc = idf_params(h, n_id, col, n_data, P)) != CFX_OK) return rc;
+    const size_t B = (size_t)P.B, nn = (size_t)P.N + 1, nu = (size_t)h->sz.nu;
+    const double* TH = id_in(h, 0, theta, (size_t)n_id * B, flags, &rc);
+    if (!TH) return rc;
+    const double* U = nu ? id_in(h, 1, u, (size_t)P.N * nu * (size_t)n_data, flags, &rc) : nullptr;
+    if (nu && !U) return rc;
+    double* F = id_out(h, 4, force, nn * B, flags, &rc);
+    if (!F) return rc;
+    double* S = sens ? id_out(h, 5, sens, nn * (size_t)n_id * B, flags, &rc) : nullptr;
+    if (sens && !S) return rc;
+    CFX_HIP(h, launch_idf_sens(h->model, h->scheme, P, TH, U, F, S, h->stream));
+    if ((rc = id_back(h, F, force, nn * B, flags)) != CFX_OK) return rc;
+    if (sens && (rc = id_back(h, S, sens, nn * (size_t)n_id * B, flags)) != CFX_OK) return rc;
+    return sync_if_host(h, flags);
+}
+
+extern "C" int cfx_idf_normal(cfx_handle* h, int32_t n_id, const int32_t* param_ids, const double* theta,
+                              const double* u, const double* target, const double* weight, int64_t n_data,
+                              double* cost, double* grad, double* gn, uint32_t flags) {
+    if (!h) {
+        g_create_error = "cfx_idf_normal: NULL handle";
+        return CFX_EINVAL;
+    }
+    int32_t col[IDF_SLOTS];
+    int rc = idf_validate(h, "cfx_idf_normal", n_id, param_ids, theta, u, n_data, col);
+    if (rc != CFX_OK) return rc;
+    if (!target || !weight) return fail(h, CFX_EINVAL, "cfx_idf_normal: target or weight is NULL");
+    if (!cost || !grad || !gn) return fail(h, CFX_EINVAL, "cfx_idf_normal: cost, grad or gn is NULL");
+    CFX_HIP(h, hipSetDevice(h->device));
+    IdfParams P;
+    if ((rc = idf_params(h, n_id, col, n_data, P)) != CFX_OK) return rc;
+    const size_t B = (size_t)P.B, nn = (size_t)P.N + 1, nu = (size_t)h->sz.nu, nd = (size_t)n_data;
+    const size_t npk = (size_t)n_id * (n_id + 1) / 2;
+    const double* TH = id_in(h, 0, theta, (size_t)n_id * B, flags, &rc);
+    if (!TH) return rc;
+    const double* U = nu ? id_in(h, 1, u, (size_t)P.N * nu * nd, flags, &rc) : nullptr;
+    if (nu && !U) return rc;
+    const double* Y = id_in(h, 2, target, nn * nd, flags, &rc);
+    if (!Y) return rc;
+    const double* W = id_in(h, 3, weight, nn * nd, flags, &rc);
+    if (!W) return rc;
+    double* C = id_out(h, 6, cost, B, flags, &rc);
+    if (!C) return rc;
+    double* G = id_out(h, 7, grad, (size_t)n_id * B, flags, &rc);
+    if (!G) return rc;
+    double* H = id_out(h, 8, gn, npk * B, flags, &rc);
+    if (!H) return rc;
+    CFX_HIP(h, launch_idf_normal(h->model, h->scheme, P, TH, U, Y, W, C, G, H, h->stream));
     if ((rc = id_back(h, C, cost, B, flags)) != CFX_OK) return rc;
     if ((rc = id_back(h, G, grad, (size_t)n_id * B, flags)) != CFX_OK) return rc;
     if ((rc = id_back(h, H, gn, npk * B, flags)) != CFX_OK) return rc;

@@ -7,6 +7,10 @@ from the rest state, is solved by a batched, box-projected Levenberg-Marquardt o
 iteration is ONE ``cfx_id_normal`` launch (cost, gradient and Gauss-Newton matrix of every start, one GPU thread
 each), followed by batched torch operations on the device for the tiny n_id x n_id damped solves, the gain ratio
 and the damping update.  Models: Ding2003, Ding2007 and Hmed2018 without fatigue.
+
+``FesFatigueIdentification`` is step 2 of the published protocol: with the force parameters fixed (the model's own
+values), the four fatigue parameters alpha_a, alpha_tau1, alpha_km, tau_fat of a ``*WithFatigue`` model are fitted to
+a fatiguing train the same way, one ``cfx_idf_normal`` launch per iteration.
 """
 
 from __future__ import annotations
@@ -126,29 +130,15 @@ def lm_solve(normal, theta0, lo, hi, max_iter=100, gtol=1e-8, xtol=1e-10, mu0=1e
     return (xT * scale.T).T, c, iters, status, torch.stack(history)
 
 
-class FesIdentification:
-    """Force-parameter identification of one muscle from one measured force curve, over ``n_starts`` starts.
+class _MultistartIdentification:
+    """What the two identification problems share: input checks, seeded starts, evaluation, the multistart fit.  A
+    subclass names its parameter ids and libcfx calls and builds ``defaults`` {key: (guess, min, max)}."""
 
-    ``force_tracking``: the measured force at every node (n_shooting + 1 values, n_shooting from
-    ``OcpFes.prepare_n_shooting``); ``key_parameter_to_identify``: keys of ``model.identifiable_parameters``;
-    ``pulse_width`` / ``pulse_intensity``: ``{"fixed": value or one value per pulse}`` as the reference's OcpFesId;
-    ``bounds``: ``{key: (min, max)}`` and ``initial_guess``: ``{key: value}`` override the reference's defaults
-    (``DEFAULT_VALUES``); start 0 is the initial guess, every other start draws each parameter log-uniformly within
-    a factor ``exp(start_spread)`` of it (seeded), clipped to the bounds; ``weight``: per-node weights (default 1).
-    """
+    _PARAM_IDS = _cfx.PARAM_IDS
+    _CHECK, _FORCES, _NORMAL = "cfx_id_check", "id_forces", "id_normal"
 
-    def __init__(self, model=None, stim_time=None, final_time=None, force_tracking=None,
-                 key_parameter_to_identify=None, pulse_width=None, pulse_intensity=None,
-                 ode_solver=OdeSolver.RK4(n_integration_steps=10), bounds=None, initial_guess=None, n_starts=64,
-                 seed=0, start_spread=0.5, weight=None, device=0):
-        if not isinstance(model, FesModel):
-            raise TypeError("model must be a FesModel type")
-        if model._with_fatigue:
-            raise ValueError("The given model is not valid and should not be including the fatigue equation in the "
-                             "model")
-        model = copy.deepcopy(model)  # the caller's model is left as it is (stim_time, stimulation history)
-        self.family = _family(model)
-        defaults = DEFAULT_VALUES[self.family]
+    def _setup(self, model, defaults, stim_time, final_time, force_tracking, key_parameter_to_identify, pulse_width,
+               pulse_intensity, ode_solver, bounds, initial_guess, n_starts, seed, start_spread, weight, device):
         if not isinstance(key_parameter_to_identify, list):
             raise TypeError(f"The given key_parameter_to_identify must be list type,"
                             f" the given value is {type(key_parameter_to_identify)} type")
@@ -194,7 +184,7 @@ class FesIdentification:
             raise ValueError("stim_time must be given, here or in the model")
         self.model = model
         self.keys = list(key_parameter_to_identify)
-        self.param_ids = [_cfx.PARAM_IDS[k] for k in self.keys]
+        self.param_ids = [self._PARAM_IDS[k] for k in self.keys]
         self._ivp = IvpFes(fes, {"final_time": final_time, "ode_solver": ode_solver})
         self.n_shooting, self.final_time = self._ivp.n_shooting, final_time
         if len(force_tracking) != self.n_shooting + 1:
@@ -219,7 +209,8 @@ class FesIdentification:
         ids = np.asarray(self.param_ids, dtype=np.int32)
         import ctypes as C
 
-        rc = lib.cfx_id_check(model.cfx_model_id, ids.size, ids.ctypes.data_as(C.POINTER(C.c_int32)))
+        check = getattr(lib, self._CHECK)
+        rc = check(model.cfx_model_id, ids.size, ids.ctypes.data_as(C.POINTER(C.c_int32)))
         if rc != _cfx.OK:
             raise _cfx.CfxError(rc, lib.cfx_last_error(None).decode())
         self._handles = {}
@@ -251,7 +242,8 @@ class FesIdentification:
         else:
             theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(len(self.keys), -1)
             B, u = theta.shape[1], (self.controls if self.controls.size else None)
-        force, sens = self._handle(B).id_forces(self.param_ids, theta, u=u, n_data=1, with_sens=with_sensitivities)
+        call = getattr(self._handle(B), self._FORCES)
+        force, sens = call(self.param_ids, theta, u=u, n_data=1, with_sens=with_sensitivities)
         return (force, sens) if with_sensitivities else force
 
     def solve(self, max_iter=100, gtol=1e-8, xtol=1e-10):
@@ -261,7 +253,7 @@ class FesIdentification:
         import torch
 
         dev = torch.device("cuda", self.device)
-        h = self._handle(self.n_starts)
+        call = getattr(self._handle(self.n_starts), self._NORMAL)
         n, B = len(self.keys), self.n_starts
         on = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)  # noqa: E731
         y, w = on(self.target), on(self.weight)
@@ -271,7 +263,7 @@ class FesIdentification:
         gn = torch.empty((n * (n + 1) // 2, B), dtype=torch.float64, device=dev)
 
         def normal(theta):
-            return h.id_normal(self.param_ids, theta.contiguous(), y, w, u=u, n_data=1, cost=cost, grad=grad, gn=gn)
+            return call(self.param_ids, theta.contiguous(), y, w, u=u, n_data=1, cost=cost, grad=grad, gn=gn)
 
         with torch.cuda.device(dev):
             theta, c, iters, status, hist = lm_solve(
@@ -300,3 +292,62 @@ class FesIdentification:
             self.close()
         except Exception:
             pass
+
+
+class FesIdentification(_MultistartIdentification):
+    """Force-parameter identification of one muscle from one measured force curve, over ``n_starts`` starts.
+
+    ``force_tracking``: the measured force at every node (n_shooting + 1 values, n_shooting from
+    ``OcpFes.prepare_n_shooting``); ``key_parameter_to_identify``: keys of ``model.identifiable_parameters``;
+    ``pulse_width`` / ``pulse_intensity``: ``{"fixed": value or one value per pulse}`` as the reference's OcpFesId;
+    ``bounds``: ``{key: (min, max)}`` and ``initial_guess``: ``{key: value}`` override the reference's defaults
+    (``DEFAULT_VALUES``); start 0 is the initial guess, every other start draws each parameter log-uniformly within
+    a factor ``exp(start_spread)`` of it (seeded), clipped to the bounds; ``weight``: per-node weights (default 1).
+    """
+
+    def __init__(self, model=None, stim_time=None, final_time=None, force_tracking=None,
+                 key_parameter_to_identify=None, pulse_width=None, pulse_intensity=None,
+                 ode_solver=OdeSolver.RK4(n_integration_steps=10), bounds=None, initial_guess=None, n_starts=64,
+                 seed=0, start_spread=0.5, weight=None, device=0):
+        if not isinstance(model, FesModel):
+            raise TypeError("model must be a FesModel type")
+        if model._with_fatigue:
+            raise ValueError("The given model is not valid and should not be including the fatigue equation in the "
+                             "model")
+        model = copy.deepcopy(model)  # the caller's model is left as it is (stim_time, stimulation history)
+        self.family = _family(model)
+        defaults = DEFAULT_VALUES[self.family]
+        self._setup(model, defaults, stim_time, final_time, force_tracking, key_parameter_to_identify, pulse_width,
+                    pulse_intensity, ode_solver, bounds, initial_guess, n_starts, seed, start_spread, weight, device)
+
+
+FATIGUE_KEYS = ("alpha_a", "alpha_tau1", "alpha_km", "tau_fat")
+
+
+class FesFatigueIdentification(_MultistartIdentification):
+    """Fatigue-parameter identification of one muscle from one measured force curve of a fatiguing train, over
+    ``n_starts`` starts: step 2 of the protocol, after ``FesIdentification`` on the fresh muscle.
+
+    ``model``: a ``*WithFatigue`` model holding the identified force parameters, which stay fixed;
+    ``key_parameter_to_identify``: keys among alpha_a, alpha_tau1, alpha_km, tau_fat (a key left out keeps the
+    model's value).  Default initial guess: the model's own value; default bounds: 0.01 x to 100 x that value, in
+    increasing order (alpha_a is negative); both can be overridden.  Every other argument, ``starts``, ``forces``,
+    ``solve`` and ``close`` are as ``FesIdentification``; the trajectory starts from the fatigue rest state."""
+
+    _PARAM_IDS = _cfx.FATIGUE_PARAM_IDS
+    _CHECK, _FORCES, _NORMAL = "cfx_idf_check", "idf_forces", "idf_normal"
+
+    def __init__(self, model=None, stim_time=None, final_time=None, force_tracking=None,
+                 key_parameter_to_identify=None, pulse_width=None, pulse_intensity=None,
+                 ode_solver=OdeSolver.RK4(n_integration_steps=10), bounds=None, initial_guess=None, n_starts=64,
+                 seed=0, start_spread=0.5, weight=None, device=0):
+        if not isinstance(model, FesModel):
+            raise TypeError("model must be a FesModel type")
+        if not model._with_fatigue:
+            raise ValueError("The given model is not valid and should be including the fatigue equation in the model")
+        model = copy.deepcopy(model)  # the caller's model is left as it is (stim_time, stimulation history)
+        self.family = _family(model)
+        own = model.identifiable_parameters
+        defaults = {k: (own[k], *sorted((0.01 * own[k], 100.0 * own[k]))) for k in FATIGUE_KEYS}
+        self._setup(model, defaults, stim_time, final_time, force_tracking, key_parameter_to_identify, pulse_width,
+                    pulse_intensity, ode_solver, bounds, initial_guess, n_starts, seed, start_spread, weight, device)

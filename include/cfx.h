@@ -267,6 +267,22 @@ int cfx_id_normal(cfx_handle *h, int32_t n_id, const int32_t *param_ids, const d
                   const double *target, const double *weight, int64_t n_data, double *cost, double *grad, double *gn,
                   uint32_t flags);
 
+/* ---- fatigue-parameter identification (step 2 of the identification protocol) ----
+   The force parameters are fixed (the handle's constants) and the four fatigue parameters are PER-INSTANCE values:
+   n_id (1..4) identified parameters, param_ids [n_id] (host array, CFX_FP_*, distinct), theta [n_id][B]; a fatigue
+   parameter that is not listed is the handle's constant.  Single shooting (RK1 / RK2 / RK4) from the fatigue rest
+   state [0, 0, A_rest (Ding2007: a_scale), tau1_rest, km_rest] of Ding2003, Ding2007 or Hmed2018 WITH fatigue; a
+   model without fatigue: CFX_EUNSUPPORTED.  Everything else (buffers, layouts, n_data, u, target, weight, force,
+   sens, cost, grad, gn, flags, the handle kinds refused) is as cfx_id_forces / cfx_id_normal / cfx_id_check. */
+enum { CFX_FP_ALPHA_A = 0, CFX_FP_ALPHA_TAU1 = 1, CFX_FP_ALPHA_KM = 2, CFX_FP_TAU_FAT = 3 };
+#define CFX_IDF_MAX_PARAMS 4
+int cfx_idf_check(int32_t model, int32_t n_id, const int32_t *param_ids);
+int cfx_idf_forces(cfx_handle *h, int32_t n_id, const int32_t *param_ids, const double *theta, const double *u,
+                   int64_t n_data, double *force, double *sens /* may be NULL */, uint32_t flags);
+int cfx_idf_normal(cfx_handle *h, int32_t n_id, const int32_t *param_ids, const double *theta, const double *u,
+                   const double *target, const double *weight, int64_t n_data, double *cost, double *grad,
+                   double *gn, uint32_t flags);
+
 /* ---- musculoskeletal problems (FesMskModel + OcpFesMsk) --------------------------------------------
    Replaces the bioptim dynamics plugin FesMskModel registers (cocofest/models/dynamical_model.py:133-203,
    406-451: every muscle's FES ODE scaled by the De Groote force-length / force-velocity / passive-force
