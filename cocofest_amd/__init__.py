@@ -21,7 +21,7 @@ from .fes_models import (
 )
 from .fourier import FourierSeries
 from .identification import FesFatigueIdentification, FesIdentification
-from .ivp import IvpFes
+from .ivp import IvpFes, IvpSweep
 from .msk import FesMskModel, FesMskOcp, OcpFesMsk
 from .nmpc import FesNmpc, NmpcFesMsk, NmpcResult
 from .ocp import Axis, Constraint, ConstraintFcn, ConstraintList, FesOcp, Node, Objective, ObjectiveFcn, ObjectiveList, OcpFes
@@ -32,6 +32,6 @@ __all__ = [
     "CfxError", "Handle", "load_library", "DingModelFrequency", "DingModelFrequencyWithFatigue",
     "DingModelPulseIntensityFrequency", "DingModelPulseIntensityFrequencyWithFatigue",
     "DingModelPulseWidthFrequency", "DingModelPulseWidthFrequencyWithFatigue", "FesModel", "ModelMaker",
-    "FourierSeries", "FesIdentification", "FesFatigueIdentification", "IvpFes", "FesOcp", "Axis", "Constraint", "ConstraintFcn", "ConstraintList", "Node", "Objective", "ObjectiveFcn", "ObjectiveList", "OcpFes",
+    "FourierSeries", "FesIdentification", "FesFatigueIdentification", "IvpFes", "IvpSweep", "FesOcp", "Axis", "Constraint", "ConstraintFcn", "ConstraintList", "Node", "Objective", "ObjectiveFcn", "ObjectiveList", "OcpFes",
     "ControlType", "OdeSolver", "FesMskModel", "FesMskOcp", "OcpFesMsk", "FesNmpc", "NmpcFesMsk", "NmpcResult", "BatchedIpm", "IpmOptions", "IpmResult", "Solver",
 ]

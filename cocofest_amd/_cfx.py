@@ -174,6 +174,11 @@ class NlpDesc(C.Structure):
                 ("hip_stream", C.c_void_p)]
 
 
+class SweepTrains(C.Structure):
+    _fields_ = [("times", C.c_void_p), ("act_node", C.c_void_p), ("value", C.c_void_p), ("n_pulses", C.c_void_p),
+                ("truncation", C.c_void_p), ("n_shooting", C.c_void_p), ("final_time", C.c_void_p)]
+
+
 # exported symbols and their signatures (must match include/cfx.h)
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
@@ -227,6 +232,13 @@ SIGNATURES = {
     "cfx_ipm_n_fixed": (C.c_int, [_P]),
     "cfx_ipm_last_error": (C.c_char_p, [_P]),
     "cfx_ipm_destroy": (None, [_P]),
+    "cfx_sweep_create": (C.c_int, [C.c_int32, C.POINTER(Constants), C.c_int32, C.c_int32, C.c_int64, C.c_int32,
+                                   C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "cfx_sweep_check": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                  C.POINTER(SweepTrains)]),
+    "cfx_sweep_integrate": (C.c_int, [_P, C.POINTER(SweepTrains), _P, _P, _P, C.c_uint32, _P]),
+    "cfx_sweep_last_error": (C.c_char_p, [_P]),
+    "cfx_sweep_destroy": (None, [_P]),
 }
 
 _lib = None
@@ -906,6 +918,110 @@ class Ipm:
         if getattr(self, "s", None):
             self.lib.cfx_ipm_destroy(self.s)
             self.s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_SWEEP_FIELDS = (("times", "float64", True), ("act_node", "int32", True), ("value", "float64", True),
+                 ("n_pulses", "int32", False), ("truncation", "int32", False), ("n_shooting", "int32", False),
+                 ("final_time", "float64", False))
+
+
+def _sweep_trains(trains: dict, batch, max_pulses, needs_value, device=None):
+    """cfx_sweep_trains over C-contiguous numpy arrays (device None) or CUDA tensors: (P, B) per-pulse arrays, (B,)
+    per-instance arrays.  Returns (struct, arrays kept alive)."""
+    st, keep = SweepTrains(), []
+    for name, dtype, per_pulse in _SWEEP_FIELDS:
+        a = trains.get(name)
+        if a is None:
+            if name == "value" and not needs_value:
+                continue
+            raise CfxError(EINVAL, f"sweep: trains[{name!r}] is missing")
+        shape = (max_pulses, batch) if per_pulse else (batch,)
+        if device is None:
+            a = np.ascontiguousarray(a, dtype=dtype)
+        elif not (_is_tensor(a) and a.is_cuda and a.device.index == device and a.is_contiguous()
+                  and str(a.dtype) == "torch." + dtype):
+            raise CfxError(EINVAL, f"sweep: trains[{name!r}] must be a contiguous {dtype} tensor on cuda:{device}")
+        if tuple(a.shape) != shape:
+            raise CfxError(EINVAL, f"sweep: trains[{name!r}] must have shape {shape}, not {tuple(a.shape)}")
+        keep.append(a)
+        setattr(st, name, _ptr(a))
+    return st, keep
+
+
+def sweep_check(model_id, scheme, n_steps, batch, max_pulses, max_shooting, trains: dict | None = None):
+    """cfx_sweep_check: the argument checks of ``Sweep`` and of its host arrays, without a device.  Raises
+    ``CfxError`` with the library's message."""
+    lib = load_library()
+    st = None
+    if trains is not None:
+        needs_value = model_id >= MODEL_IDS["ding2007"]
+        st, _keep = _sweep_trains(trains, batch, max_pulses, needs_value)
+    rc = lib.cfx_sweep_check(model_id, scheme, n_steps, batch, max_pulses, max_shooting,
+                             None if st is None else C.byref(st))
+    if rc != OK:
+        raise CfxError(rc, lib.cfx_last_error(None).decode())
+
+
+class Sweep:
+    """One cfx_sweep: single shooting of B instances of one model, every instance with its own stimulation train
+    (``trains``: the arrays of ``cfx_sweep_trains``, SoA).  Host numpy arrays are checked, copied and the call
+    returns when the results are back; CUDA tensors are used in place, unchecked, on torch's current stream."""
+
+    def __init__(self, *, model_id, constants: dict, scheme, n_steps, batch, max_pulses, max_shooting, device=0):
+        self.lib = load_library()
+        cst = Constants()
+        for name, _ in Constants._fields_:
+            setattr(cst, name, float(constants.get(name, 0.0)))
+        h = C.c_void_p()
+        rc = self.lib.cfx_sweep_create(model_id, C.byref(cst), scheme, n_steps, batch, max_pulses, max_shooting,
+                                       device, C.byref(h))
+        if rc != OK:
+            raise CfxError(rc, self.lib.cfx_last_error(None).decode())
+        self.h = h
+        self.model_id, self.batch, self.max_pulses, self.max_shooting = model_id, batch, max_pulses, max_shooting
+        self.device = device
+        self.nx = 5 if model_id & 1 else 2
+        self.needs_value = model_id >= MODEL_IDS["ding2007"]
+
+    def integrate(self, trains: dict, x0=None, nodes=False):
+        """Final states (nx, B) and, with ``nodes``, the node states (max_shooting + 1, nx, B) (NaN past an
+        instance's own n_shooting); ``x0``: (nx, B) or None (the rest state).  Returns (final, nodes or None)."""
+        B, nx = self.batch, self.nx
+        on_device = _is_tensor(trains.get("times"))
+        st, keep = _sweep_trains(trains, B, self.max_pulses, self.needs_value, self.device if on_device else None)
+        if on_device:
+            import torch
+
+            dev = f"cuda:{self.device}"
+            if x0 is not None and not (_is_tensor(x0) and x0.is_cuda and x0.dtype == torch.float64
+                                       and x0.is_contiguous() and tuple(x0.shape) == (nx, B)):
+                raise CfxError(EINVAL, f"sweep: x0 must be a contiguous float64 ({nx}, {B}) tensor on {dev}")
+            final = torch.empty((nx, B), dtype=torch.float64, device=dev)
+            out = torch.empty((self.max_shooting + 1, nx, B), dtype=torch.float64, device=dev) if nodes else None
+            stream, fl = torch.cuda.current_stream().cuda_stream, DEVICE
+        else:
+            if x0 is not None:
+                x0 = np.ascontiguousarray(x0, dtype=np.float64)
+                if x0.shape != (nx, B):
+                    raise CfxError(EINVAL, f"sweep: x0 must have shape ({nx}, {B}), not {x0.shape}")
+            final = np.empty((nx, B))
+            out = np.empty((self.max_shooting + 1, nx, B)) if nodes else None
+            stream, fl = None, 0
+        rc = self.lib.cfx_sweep_integrate(self.h, C.byref(st), _ptr(x0), _ptr(final), _ptr(out), fl, stream)
+        if rc != OK:
+            raise CfxError(rc, self.lib.cfx_sweep_last_error(self.h).decode())
+        return final, out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.cfx_sweep_destroy(self.h)
+            self.h = None
 
     def __del__(self):
         try:

@@ -18,6 +18,7 @@
 #include "cfx_internal.h"
 #include "cfx_launch.h"
 #include "cfx_msk_launch.h"
+#include "cfx_sweep.h"
 
 using namespace cfx;
 
@@ -2313,6 +2314,233 @@ __global__ void __launch_bounds__(256) k_gather_sum(int64_t batch, int64_t n_dst
     double acc = 0.0;
     for (int32_t s = ptr[i]; s < ptr[i + 1]; ++s) acc += src[b * src_len + idx[s]];
     dst[b * n_dst + i] = acc;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// stimulation-train sweeps (cfx_sweep.h): every instance carries its own train
+// ------------------------------------------------------------------------------------------------------
+struct cfx_sweep {
+    int model = 0, scheme = 1, nx = 2, device = 0;
+    int64_t B = 0;
+    int32_t P = 0, Nmax = 0, m = 1;
+    bool needs_value = false;
+    SweepParams sp{};
+    hipStream_t stream = nullptr;
+    // staging of host calls: times, value, final_time, x0, xf, nodes (doubles); act + the three counts (int32)
+    DevBuf dbuf[6];
+    int32_t* d_int = nullptr;
+    std::string err;
+};
+
+// The argument checks of cfx_sweep_create and (tr != nullptr) of the host arrays of cfx_sweep_integrate.
+static int sweep_check(const char* fn, int model, int scheme, int n_steps, int64_t B, int P, int Nmax,
+                       const cfx_sweep_trains* tr, std::string& msg) {
+    const std::string f = std::string(fn) + ": ";
+    if (model < CFX_DING2003 || model > CFX_HMED2018_FATIGUE) return msg = f + "unknown model", CFX_EINVAL;
+    if (scheme != CFX_RK1 && scheme != CFX_RK2 && scheme != CFX_RK4)
+        return msg = f + "unknown scheme (must be CFX_RK1, CFX_RK2 or CFX_RK4)", CFX_EINVAL;
+    if (n_steps < 1 || B < 1 || P < 1 || Nmax < 1)
+        return msg = f + "n_steps, batch, max_pulses and max_shooting must be positive", CFX_EINVAL;
+    if (Nmax > kMaxGridY) return msg = f + "max_shooting must be <= 65535", CFX_EINVAL;
+    if (!tr) return CFX_OK;
+    const bool needs_value = is_pw(model) || is_int(model);
+    if (!tr->times || !tr->act_node || !tr->n_pulses || !tr->truncation || !tr->n_shooting || !tr->final_time ||
+        (needs_value && !tr->value))
+        return msg = f + "a train array is NULL", CFX_EINVAL;
+    for (int64_t b = 0; b < B; ++b) {
+        const std::string at = f + "instance " + std::to_string(b) + ": ";
+        const int N = tr->n_shooting[b], np = tr->n_pulses[b];
+        if (N > kMaxGridY) return msg = at + "n_shooting must be <= 65535", CFX_EINVAL;
+        if (N < 1 || N > Nmax) return msg = at + "n_shooting must be in [1, max_shooting]", CFX_EINVAL;
+        if (tr->truncation[b] < 1) return msg = at + "truncation must be >= 1", CFX_EINVAL;
+        if (np < 0 || np > P) return msg = at + "n_pulses must be in [0, max_pulses]", CFX_EINVAL;
+        if (!(tr->final_time[b] > 0.0) || !std::isfinite(tr->final_time[b]))
+            return msg = at + "final_time must be positive and finite", CFX_EINVAL;
+        for (int i = 0; i < np; ++i) {
+            const std::string pi = at + "pulse " + std::to_string(i) + ": ";
+            const double t = tr->times[(int64_t)i * B + b];
+            const int a = tr->act_node[(int64_t)i * B + b];
+            if (!std::isfinite(t)) return msg = pi + "time is not finite", CFX_EINVAL;
+            if (i > 0 && t < tr->times[(int64_t)(i - 1) * B + b]) return msg = pi + "time decreases", CFX_EINVAL;
+            if (a < 0) return msg = pi + "activation node is negative", CFX_EINVAL;
+            if (a > N) return msg = pi + "activation node past n_shooting", CFX_EINVAL;
+            if (i > 0 && a < tr->act_node[(int64_t)(i - 1) * B + b])
+                return msg = pi + "activation node decreases", CFX_EINVAL;
+            if (needs_value && !std::isfinite(tr->value[(int64_t)i * B + b]))
+                return msg = pi + "value is not finite", CFX_EINVAL;
+        }
+    }
+    return CFX_OK;
+}
+
+extern "C" int cfx_sweep_check(int32_t model, int32_t scheme, int32_t n_steps, int64_t batch, int32_t max_pulses,
+                               int32_t max_shooting, const cfx_sweep_trains* trains) {
+    return sweep_check("cfx_sweep_check", model, scheme, n_steps, batch, max_pulses, max_shooting, trains,
+                       g_create_error);
+}
+
+extern "C" void cfx_sweep_destroy(cfx_sweep* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    if (s->stream) (void)hipStreamSynchronize(s->stream);
+    for (DevBuf& b : s->dbuf)
+        if (b.p) (void)hipFree(b.p);
+    if (s->d_int) (void)hipFree(s->d_int);
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    delete s;
+}
+
+extern "C" const char* cfx_sweep_last_error(const cfx_sweep* s) { return s ? s->err.c_str() : g_create_error.c_str(); }
+
+extern "C" int cfx_sweep_create(int32_t model, const cfx_constants* c, int32_t scheme, int32_t n_steps, int64_t batch,
+                                int32_t max_pulses, int32_t max_shooting, int32_t device, cfx_sweep** out) {
+    if (!c || !out) return g_create_error = "cfx_sweep_create: NULL argument", CFX_EINVAL;
+    *out = nullptr;
+    int rc = sweep_check("cfx_sweep_create", model, scheme, n_steps, batch, max_pulses, max_shooting, nullptr,
+                         g_create_error);
+    if (rc != CFX_OK) return rc;
+    if (!(c->tauc > 0.0)) return g_create_error = "cfx_sweep_create: tauc must be positive", CFX_EINVAL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return g_create_error = "cfx_sweep_create: no HIP device available (libcfx has no CPU path)", CFX_ENODEV;
+    if (device < 0 || device >= ndev) return g_create_error = "cfx_sweep_create: bad device ordinal", CFX_ENODEV;
+    cfx_sweep* s = new cfx_sweep();
+    s->model = model;
+    s->scheme = scheme;
+    s->nx = is_fatigue(model) ? 5 : 2;
+    s->device = device;
+    s->B = batch;
+    s->P = max_pulses;
+    s->Nmax = max_shooting;
+    s->m = n_steps;
+    s->needs_value = is_pw(model) || is_int(model);
+    SweepParams& sp = s->sp;
+    sp.B = batch;
+    sp.P = max_pulses;
+    sp.Nmax = max_shooting;
+    sp.m = n_steps;
+    sp.inv_tauc = 1.0 / c->tauc;
+    sp.r0m1 = c->km_rest + c->r0_km_relationship - 1.0;
+    sp.mult = c->fl * c->fv + c->fp;
+    sp.tau2 = c->tau2;
+    sp.a_rest = is_pw(model) ? c->a_scale : c->a_rest;
+    sp.tau1_rest = c->tau1_rest;
+    sp.km_rest = c->km_rest;
+    sp.pd0 = c->pd0;
+    sp.inv_pdt = is_pw(model) ? 1.0 / c->pdt : 0.0;
+    sp.ar = c->ar;
+    sp.bs = c->bs;
+    sp.Is = c->Is;
+    sp.cr = c->cr;
+    sp.alpha_a = c->alpha_a;
+    sp.alpha_tau1 = c->alpha_tau1;
+    sp.alpha_km = c->alpha_km;
+    sp.inv_tau_fat = is_fatigue(model) ? 1.0 / c->tau_fat : 0.0;
+    if (hipSetDevice(device) != hipSuccess ||
+        hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
+        s->stream = nullptr;
+        cfx_sweep_destroy(s);
+        return g_create_error = "cfx_sweep_create: could not create a stream on the device", CFX_EHIP;
+    }
+    *out = s;
+    return CFX_OK;
+}
+
+static int sweep_fail(cfx_sweep* s, int code, const std::string& msg) {
+    s->err = msg;
+    return code;
+}
+
+// device buffer `slot` of at least n doubles
+static double* sweep_buf(cfx_sweep* s, int slot, size_t n, int* rc) {
+    DevBuf& b = s->dbuf[slot];
+    if (b.n < n) {
+        if (b.p) (void)hipFree(b.p);
+        b.p = nullptr;
+        b.n = 0;
+        if (hipMalloc(&b.p, n * sizeof(double)) != hipSuccess) {
+            b.p = nullptr;
+            *rc = sweep_fail(s, CFX_ENOMEM, "cfx_sweep_integrate: hipMalloc failed");
+            return nullptr;
+        }
+        b.n = n;
+    }
+    return b.p;
+}
+
+extern "C" int cfx_sweep_integrate(cfx_sweep* s, const cfx_sweep_trains* tr, const double* x0, double* final_state,
+                                   double* nodes, uint32_t flags, void* hip_stream) {
+    if (!s) return g_create_error = "cfx_sweep_integrate: NULL handle", CFX_EINVAL;
+    if (!tr || !final_state) return sweep_fail(s, CFX_EINVAL, "cfx_sweep_integrate: trains or final_state is NULL");
+    if (!tr->times || !tr->act_node || !tr->n_pulses || !tr->truncation || !tr->n_shooting || !tr->final_time ||
+        (s->needs_value && !tr->value))
+        return sweep_fail(s, CFX_EINVAL, "cfx_sweep_integrate: a train array is NULL");
+    const size_t B = (size_t)s->B, P = (size_t)s->P, nx = (size_t)s->nx, nn = (size_t)s->Nmax + 1;
+    SweepParams sp = s->sp;
+    if (hipSetDevice(s->device) != hipSuccess) return sweep_fail(s, CFX_EHIP, "cfx_sweep_integrate: hipSetDevice failed");
+    if (flags & CFX_DEVICE) {
+        sp.times = tr->times;
+        sp.act = tr->act_node;
+        sp.value = tr->value;
+        sp.n_pulses = tr->n_pulses;
+        sp.truncation = tr->truncation;
+        sp.n_shooting = tr->n_shooting;
+        sp.final_time = tr->final_time;
+        sp.x0 = x0;
+        sp.xf = final_state;
+        sp.nodes = nodes;
+        const hipError_t e = launch_sweep(s->model, s->scheme, sp, (hipStream_t)hip_stream);
+        if (e != hipSuccess) return sweep_fail(s, CFX_EHIP, std::string("cfx_sweep_integrate: ") + hipGetErrorString(e));
+        return CFX_OK;
+    }
+    int rc = sweep_check("cfx_sweep_integrate", s->model, s->scheme, s->m, s->B, s->P, s->Nmax, tr, s->err);
+    if (rc != CFX_OK) return rc;
+    if (x0)
+        for (size_t i = 0; i < nx * B; ++i)
+            if (!std::isfinite(x0[i])) return sweep_fail(s, CFX_EINVAL, "cfx_sweep_integrate: x0 is not finite");
+    double* d_t = sweep_buf(s, 0, P * B, &rc);
+    double* d_v = s->needs_value ? sweep_buf(s, 1, P * B, &rc) : nullptr;
+    double* d_tf = sweep_buf(s, 2, B, &rc);
+    double* d_x0 = x0 ? sweep_buf(s, 3, nx * B, &rc) : nullptr;
+    double* d_xf = sweep_buf(s, 4, nx * B, &rc);
+    double* d_nd = nodes ? sweep_buf(s, 5, nn * nx * B, &rc) : nullptr;
+    if (!d_t || (s->needs_value && !d_v) || !d_tf || (x0 && !d_x0) || !d_xf || (nodes && !d_nd)) return rc;
+    if (!s->d_int && hipMalloc(&s->d_int, (P + 3) * B * sizeof(int32_t)) != hipSuccess) {
+        s->d_int = nullptr;
+        return sweep_fail(s, CFX_ENOMEM, "cfx_sweep_integrate: hipMalloc failed");
+    }
+    int32_t* d_act = s->d_int;
+    int32_t* d_cnt = s->d_int + P * B;
+    hipStream_t st = s->stream;
+#define SWEEP_HIP(call)                                                                          \
+    do {                                                                                         \
+        hipError_t e_ = (call);                                                                  \
+        if (e_ != hipSuccess) return sweep_fail(s, CFX_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+    SWEEP_HIP(hipMemcpyAsync(d_t, tr->times, P * B * sizeof(double), hipMemcpyHostToDevice, st));
+    if (d_v) SWEEP_HIP(hipMemcpyAsync(d_v, tr->value, P * B * sizeof(double), hipMemcpyHostToDevice, st));
+    SWEEP_HIP(hipMemcpyAsync(d_tf, tr->final_time, B * sizeof(double), hipMemcpyHostToDevice, st));
+    if (d_x0) SWEEP_HIP(hipMemcpyAsync(d_x0, x0, nx * B * sizeof(double), hipMemcpyHostToDevice, st));
+    SWEEP_HIP(hipMemcpyAsync(d_act, tr->act_node, P * B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    SWEEP_HIP(hipMemcpyAsync(d_cnt, tr->n_pulses, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    SWEEP_HIP(hipMemcpyAsync(d_cnt + B, tr->truncation, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    SWEEP_HIP(hipMemcpyAsync(d_cnt + 2 * B, tr->n_shooting, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    sp.times = d_t;
+    sp.act = d_act;
+    sp.value = d_v;
+    sp.n_pulses = d_cnt;
+    sp.truncation = d_cnt + B;
+    sp.n_shooting = d_cnt + 2 * B;
+    sp.final_time = d_tf;
+    sp.x0 = d_x0;
+    sp.xf = d_xf;
+    sp.nodes = d_nd;
+    SWEEP_HIP(launch_sweep(s->model, s->scheme, sp, st));
+    SWEEP_HIP(hipMemcpyAsync(final_state, d_xf, nx * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (d_nd) SWEEP_HIP(hipMemcpyAsync(nodes, d_nd, nn * nx * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    SWEEP_HIP(hipStreamSynchronize(st));
+#undef SWEEP_HIP
+    return CFX_OK;
 }
 
 extern "C" int cfx_gather_sum(int64_t batch, int64_t n_dst, const int32_t* ptr, const int32_t* idx, const double* src,

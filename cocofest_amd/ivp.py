@@ -5,9 +5,14 @@ integration itself (single shooting, every RK sub-step returned) runs on the GPU
 ``cfx_integrate``; batches of independent instances use :meth:`IvpFes.handle`.  With
 ``OdeSolver.COLLOCATION`` the same call runs the implicit collocation integrator: every interval's node
 state and collocation states are returned.
+
+``IvpSweep`` integrates a list of ``IvpFes`` objects of one model in a single launch (``cfx_sweep_integrate``):
+every instance keeps its own stimulation train, truncation, ``n_shooting`` and ``final_time``.
 """
 
 from __future__ import annotations
+
+from fractions import Fraction
 
 import numpy as np
 
@@ -19,6 +24,7 @@ from .fes_models import (
     DingModelPulseWidthFrequencyWithFatigue,
     FesModel,
     PLACEHOLDER_INTENSITY,
+    PLACEHOLDER_TIME,
 )
 from .ocp import OcpFes
 from .ode_solver import OdeSolver
@@ -244,3 +250,164 @@ class IvpFes:
         ivp_parameters["final_time"] = n_stim / frequency
         fes_parameters["stim_time"] = list(np.round([i * 1 / frequency for i in range(n_stim)], 3))
         return cls(fes_parameters, ivp_parameters)
+
+
+def activation_nodes(stim_time, n_shooting: int, final_time) -> list:
+    """Per pulse, the first node k with t_i <= k final_time / n_shooting, in the exact rational arithmetic of
+    ``get_numerical_data_time_series`` (a pulse before t = 0 is visible from node 0; a value above ``n_shooting``
+    means the pulse is never visible)."""
+    tf = Fraction(final_time).limit_denominator()
+    out = []
+    for t in stim_time:
+        q = Fraction(t).limit_denominator() * n_shooting / tf
+        out.append(max(0, -((-q.numerator) // q.denominator)))  # ceil
+    return out
+
+
+def pack_train(ivp: IvpFes) -> dict:
+    """What the sweep kernel needs of one ``IvpFes``: pulse times, activation nodes, per-pulse widths (Ding2007) or
+    intensities (Hmed2018), truncation, n_shooting, final_time.  Pulses that no node sees are left out.
+
+    Ding2007: ``IvpFes._build_controls`` gives interval k the width ``pulse_width[min(v, N + 1) - 1]`` where v is the
+    number of visible pulses (the reference's ``stim_idx_at_node_list`` is cut from a list of N + 1 nodes), so pulse i
+    carries ``pulse_width[min(i, N)]``: the interval widths are the ones ``IvpFes.integrate`` uses."""
+    times = [float(t) for t in ivp.stim_time]
+    if any(b < a for a, b in zip(times, times[1:])):
+        raise ValueError("stim_time must be sorted")
+    N = int(ivp.n_shooting)
+    act = activation_nodes(ivp.stim_time, N, ivp.final_time)
+    n = sum(1 for a in act if a <= N)
+    value = None
+    if isinstance(ivp.model, DingModelPulseWidthFrequency):
+        pw = ivp.pulse_width
+        if isinstance(pw, list) and len(pw) != 1:
+            value = [float(pw[min(i, N, len(pw) - 1)]) for i in range(n)]
+        else:
+            value = [float(pw[0] if isinstance(pw, list) else pw)] * n
+    elif isinstance(ivp.model, DingModelPulseIntensityFrequency):
+        pi = ivp.pulse_intensity
+        if isinstance(pi, list) and len(pi) != 1:
+            value = [float(pi[i]) for i in range(n)]
+        else:
+            value = [float(pi[0] if isinstance(pi, list) else pi)] * n
+    return {"times": times[:n], "act_node": act[:n], "value": value, "truncation": int(ivp.model._sum_stim_truncation),
+            "n_shooting": N, "final_time": float(ivp.final_time)}
+
+
+def sweep_order(work) -> np.ndarray:
+    """Launch order of a sweep: instances sorted by their amount of work, heaviest first (stable), so that the
+    lanes of a wave finish together.  ``order[j]`` is the caller's index of packed instance j."""
+    return np.argsort(-np.asarray(work, dtype=np.int64), kind="stable")
+
+
+class IvpSweep:
+    """A batch of ``IvpFes`` problems of one model integrated in one launch, every instance with its own train.
+
+    ``ivps``: ``IvpFes`` objects of the same model class, model constants and ``ode_solver`` (RK1 / RK2 / RK4);
+    stimulation times, pulse mode, truncation, ``n_shooting``, ``final_time`` and pulse widths / intensities are
+    free per instance.  ``ValueError`` names the first instance that does not fit."""
+
+    def __init__(self, ivps, device: int = 0):
+        ivps = list(ivps)
+        if not ivps:
+            raise ValueError("IvpSweep needs at least one IvpFes")
+        first = ivps[0]
+        if not isinstance(first, IvpFes):
+            raise TypeError("IvpSweep takes a list of IvpFes")
+        solver = first.ode_solver
+        for i, ivp in enumerate(ivps):
+            if not isinstance(ivp, IvpFes):
+                raise TypeError("IvpSweep takes a list of IvpFes")
+            if isinstance(ivp.ode_solver, OdeSolver.COLLOCATION):
+                raise ValueError(f"ivps[{i}]: OdeSolver.COLLOCATION is not supported by IvpSweep")
+            if type(ivp.model) is not type(first.model):
+                raise ValueError(f"ivps[{i}]: model class {type(ivp.model).__name__} differs from "
+                                 f"{type(first.model).__name__}")
+            if ivp.model.cfx_constants() != first.model.cfx_constants():
+                raise ValueError(f"ivps[{i}]: model constants differ from ivps[0]'s")
+            if (type(ivp.ode_solver) is not type(solver)
+                    or ivp.ode_solver.n_integration_steps != solver.n_integration_steps):
+                raise ValueError(f"ivps[{i}]: ode_solver differs from ivps[0]'s")
+            if any(t != PLACEHOLDER_TIME for t in ivp.model.previous_stim["time"]):
+                raise ValueError(f"ivps[{i}]: previous_stim is not supported by IvpSweep")
+        self.model = first.model
+        self.ode_solver = solver
+        self.batch = len(ivps)
+        self.device = device
+        trains = []
+        for i, ivp in enumerate(ivps):
+            try:
+                trains.append(pack_train(ivp))
+            except ValueError as e:
+                raise ValueError(f"ivps[{i}]: {e}") from None
+        self.n_shooting = np.array([t["n_shooting"] for t in trains], dtype=np.int32)
+        m = solver.n_integration_steps
+        work = [t["n_shooting"] * m * max(1, min(t["truncation"], len(t["times"]))) for t in trains]
+        self.order = sweep_order(work)
+        self.max_pulses = max(1, max(len(t["times"]) for t in trains))
+        self.max_shooting = int(self.n_shooting.max())
+        self.trains = self._pack([trains[i] for i in self.order])
+        _cfx.sweep_check(self.model.cfx_model_id, solver.scheme, m, self.batch, self.max_pulses, self.max_shooting,
+                         self.trains)
+        self._sweep = None
+
+    def _pack(self, trains) -> dict:
+        """SoA arrays of ``cfx_sweep_trains`` in launch order."""
+        B, P = len(trains), self.max_pulses
+        with_value = trains[0]["value"] is not None
+        out = {"times": np.zeros((P, B)), "act_node": np.zeros((P, B), dtype=np.int32),
+               "value": np.zeros((P, B)) if with_value else None,
+               "n_pulses": np.array([len(t["times"]) for t in trains], dtype=np.int32),
+               "truncation": np.array([t["truncation"] for t in trains], dtype=np.int32),
+               "n_shooting": np.array([t["n_shooting"] for t in trains], dtype=np.int32),
+               "final_time": np.array([t["final_time"] for t in trains], dtype=np.float64)}
+        for b, t in enumerate(trains):
+            n = len(t["times"])
+            out["times"][:n, b] = t["times"]
+            out["act_node"][:n, b] = t["act_node"]
+            if with_value:
+                out["value"][:n, b] = t["value"]
+        return out
+
+    def sweep(self) -> _cfx.Sweep:
+        """The library object (created on first use)."""
+        if self._sweep is None:
+            self._sweep = _cfx.Sweep(model_id=self.model.cfx_model_id, constants=self.model.cfx_constants(),
+                                     scheme=self.ode_solver.scheme, n_steps=self.ode_solver.n_integration_steps,
+                                     batch=self.batch, max_pulses=self.max_pulses, max_shooting=self.max_shooting,
+                                     device=self.device)
+        return self._sweep
+
+    def integrate(self, x0=None, nodes: bool = False) -> dict:
+        """Single shooting of every instance from the rest state, or from ``x0`` ((nx,) for all, or (B, nx)).
+
+        Returns {state: (B,)}, the final states, in the order of ``ivps``.  ``nodes=True``: {state: (B, N_max + 1)},
+        the node states, NaN past an instance's own ``n_shooting``, plus ``"n_shooting"``: (B,)."""
+        nx, B = self.model.nb_state, self.batch
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=np.float64)
+            if x0.shape == (nx,):
+                x0 = np.broadcast_to(x0, (B, nx))
+            if x0.shape != (B, nx):
+                raise ValueError(f"x0 must have shape ({nx},) or ({B}, {nx})")
+            x0 = np.ascontiguousarray(x0[self.order].T)
+        final, traj = self.sweep().integrate(self.trains, x0=x0, nodes=nodes)
+        inverse = np.empty(B, dtype=np.int64)
+        inverse[self.order] = np.arange(B)
+        names = self.model.name_dof
+        if not nodes:
+            return {name: final[i, inverse].copy() for i, name in enumerate(names)}
+        result = {name: traj[:, i, :].T[inverse].copy() for i, name in enumerate(names)}
+        result["n_shooting"] = self.n_shooting.copy()
+        return result
+
+    def close(self):
+        if getattr(self, "_sweep", None) is not None:
+            self._sweep.close()
+            self._sweep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

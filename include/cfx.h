@@ -633,6 +633,46 @@ int cfx_ipm_n_fixed(const cfx_ipm *s);
 const char *cfx_ipm_last_error(const cfx_ipm *s);
 void cfx_ipm_destroy(cfx_ipm *s);
 
+/* ---- stimulation-train sweeps (batched IvpFes with PER-INSTANCE trains) ------------------------------
+   Single shooting (RK1 / RK2 / RK4 with n_steps sub-steps) of any of the six models in which every instance carries
+   its own train: the forward-simulation studies of the reference (examples/sensitivity/truncation) in one launch.
+   The calcium forcing is formed on the device from the instance's pulses, so the truncation has no upper bound here.
+   Every array is SoA (element-major, instance-minor); host pointers, or device pointers with CFX_DEVICE:
+     times [P][B]       pulse times, non-decreasing over an instance's first n_pulses entries
+     act_node [P][B]    the pulse's activation node: the first node k with t_i <= k final_time / N, decided by the
+                        caller in exact arithmetic (the kernel never compares floating-point times); >= 0,
+                        non-decreasing, <= n_shooting.  At interval k the visible pulses are those with act_node <= k
+                        and the window is the last `truncation` of them (empty window: no forcing)
+     value [P][B]       Ding2007: pulse width, Hmed2018: pulse intensity of the pulse; Ding2003: ignored, may be NULL.
+                        Ding2007's interval k uses the width of the last visible pulse (the first pulse's before any)
+     n_pulses, truncation, n_shooting [B]   0 <= n_pulses <= P, truncation >= 1, 1 <= n_shooting <= max_shooting
+     final_time [B]     > 0
+   Entries past an instance's n_pulses are not read.  P = max_pulses and max_shooting (<= 65535) are fixed at
+   creation with the model, its constants (shared by the batch), the scheme and the batch size.
+   cfx_sweep_integrate: x0 [nx][B] or NULL (the rest state); final_state [nx][B]; nodes (may be NULL)
+   [max_shooting + 1][nx][B], the node states, NaN past an instance's own n_shooting.  Host arrays are checked
+   before the launch and a violation returns CFX_EINVAL with nothing launched; with CFX_DEVICE the caller is
+   responsible for them, the call is asynchronous on `hip_stream` (NULL = the HIP null stream) and nothing is copied.
+   An instance's result does not depend on its position in the batch.
+   cfx_sweep_check: the same argument checks without a device (trains == NULL: the creation arguments only); message
+   through cfx_last_error(NULL), as are cfx_sweep_create's. */
+typedef struct cfx_sweep cfx_sweep;
+typedef struct cfx_sweep_trains {
+    const double *times;
+    const int32_t *act_node;
+    const double *value;
+    const int32_t *n_pulses, *truncation, *n_shooting;
+    const double *final_time;
+} cfx_sweep_trains;
+int cfx_sweep_create(int32_t model, const cfx_constants *constants, int32_t scheme, int32_t n_steps, int64_t batch,
+                     int32_t max_pulses, int32_t max_shooting, int32_t device, cfx_sweep **out);
+int cfx_sweep_check(int32_t model, int32_t scheme, int32_t n_steps, int64_t batch, int32_t max_pulses,
+                    int32_t max_shooting, const cfx_sweep_trains *trains);
+int cfx_sweep_integrate(cfx_sweep *s, const cfx_sweep_trains *trains, const double *x0, double *final_state,
+                        double *nodes, uint32_t flags, void *hip_stream);
+const char *cfx_sweep_last_error(const cfx_sweep *s);
+void cfx_sweep_destroy(cfx_sweep *s);
+
 /* ---- placing gathered value slices --------------------------------------------------------------------
    dst[b][i] = sum over s in [ptr[i], ptr[i+1]) of src[b][idx[s]] for the batch-major (AoS) src [batch][src_len] and
    dst [batch][n_dst] on `hip_stream` (device pointers; ptr / idx device int32 arrays): the fixed gather table that
