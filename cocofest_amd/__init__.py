@@ -20,7 +20,8 @@ from .fes_models import (
     ModelMaker,
 )
 from .fourier import FourierSeries
-from .identification import FesFatigueIdentification, FesIdentification
+from .identification import (FesFatigueIdentification, FesIdentification, FesMultiTrainIdentification,
+                             force_at_node)
 from .ivp import IvpFes, IvpSweep
 from .msk import FesMskModel, FesMskOcp, OcpFesMsk
 from .nmpc import FesNmpc, NmpcFesMsk, NmpcResult
@@ -32,6 +33,6 @@ __all__ = [
     "CfxError", "Handle", "load_library", "DingModelFrequency", "DingModelFrequencyWithFatigue",
     "DingModelPulseIntensityFrequency", "DingModelPulseIntensityFrequencyWithFatigue",
     "DingModelPulseWidthFrequency", "DingModelPulseWidthFrequencyWithFatigue", "FesModel", "ModelMaker",
-    "FourierSeries", "FesIdentification", "FesFatigueIdentification", "IvpFes", "IvpSweep", "FesOcp", "Axis", "Constraint", "ConstraintFcn", "ConstraintList", "Node", "Objective", "ObjectiveFcn", "ObjectiveList", "OcpFes",
+    "FourierSeries", "FesIdentification", "FesFatigueIdentification", "FesMultiTrainIdentification", "force_at_node", "IvpFes", "IvpSweep", "FesOcp", "Axis", "Constraint", "ConstraintFcn", "ConstraintList", "Node", "Objective", "ObjectiveFcn", "ObjectiveList", "OcpFes",
     "ControlType", "OdeSolver", "FesMskModel", "FesMskOcp", "OcpFesMsk", "FesNmpc", "NmpcFesMsk", "NmpcResult", "BatchedIpm", "IpmOptions", "IpmResult", "Solver",
 ]

@@ -179,6 +179,10 @@ class SweepTrains(C.Structure):
                 ("truncation", C.c_void_p), ("n_shooting", C.c_void_p), ("final_time", C.c_void_p)]
 
 
+class IdmTrains(C.Structure):
+    _fields_ = SweepTrains._fields_ + [("target", C.c_void_p), ("weight", C.c_void_p)]
+
+
 # exported symbols and their signatures (must match include/cfx.h)
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
@@ -239,6 +243,15 @@ SIGNATURES = {
     "cfx_sweep_integrate": (C.c_int, [_P, C.POINTER(SweepTrains), _P, _P, _P, C.c_uint32, _P]),
     "cfx_sweep_last_error": (C.c_char_p, [_P]),
     "cfx_sweep_destroy": (None, [_P]),
+    "cfx_idm_create": (C.c_int, [C.c_int32, C.POINTER(Constants), C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                 C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "cfx_idm_check": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                C.POINTER(C.c_int32), C.POINTER(IdmTrains)]),
+    "cfx_idm_forces": (C.c_int, [_P, C.POINTER(IdmTrains), C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, C.c_uint32, _P]),
+    "cfx_idm_normal": (C.c_int, [_P, C.POINTER(IdmTrains), C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, _P, _P,
+                                 C.c_uint32, _P]),
+    "cfx_idm_last_error": (C.c_char_p, [_P]),
+    "cfx_idm_destroy": (None, [_P]),
 }
 
 _lib = None
@@ -1021,6 +1034,137 @@ class Sweep:
     def close(self):
         if getattr(self, "h", None):
             self.lib.cfx_sweep_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_IDM_FIELDS = _SWEEP_FIELDS + (("target", "float64", None), ("weight", "float64", None))
+
+
+def _idm_trains(trains: dict, n_trains, max_pulses, max_shooting, needs_value, device=None):
+    """cfx_idm_trains over C-contiguous numpy arrays (device None) or CUDA tensors: (P, E) per-pulse arrays, (E,)
+    per-train arrays, (max_shooting + 1, E) target and weight (optional here).  Returns (struct, arrays kept alive)."""
+    st, keep = IdmTrains(), []
+    for name, dtype, kind in _IDM_FIELDS:
+        a = trains.get(name)
+        if a is None:
+            if (name == "value" and not needs_value) or kind is None:
+                continue
+            raise CfxError(EINVAL, f"idm: trains[{name!r}] is missing")
+        shape = {True: (max_pulses, n_trains), False: (n_trains,), None: (max_shooting + 1, n_trains)}[kind]
+        if device is None:
+            a = np.ascontiguousarray(a, dtype=dtype)
+        elif not (_is_tensor(a) and a.is_cuda and a.device.index == device and a.is_contiguous()
+                  and str(a.dtype) == "torch." + dtype):
+            raise CfxError(EINVAL, f"idm: trains[{name!r}] must be a contiguous {dtype} tensor on cuda:{device}")
+        if tuple(a.shape) != shape:
+            raise CfxError(EINVAL, f"idm: trains[{name!r}] must have shape {shape}, not {tuple(a.shape)}")
+        keep.append(a)
+        setattr(st, name, _ptr(a))
+    return st, keep
+
+
+def _idm_ids(param_ids):
+    ids = np.ascontiguousarray(param_ids, dtype=np.int32).reshape(-1)
+    return ids, ids.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def idm_check(model_id, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, param_ids, trains: dict | None = None):
+    """cfx_idm_check: the argument checks of ``Idm`` and of its host arrays, without a device.  Raises ``CfxError``
+    with the library's message."""
+    lib = load_library()
+    st = None
+    if trains is not None:
+        st, _keep = _idm_trains(trains, n_trains, max_pulses, max_shooting, model_id >= MODEL_IDS["ding2007"])
+    ids, idp = _idm_ids(param_ids)
+    rc = lib.cfx_idm_check(model_id, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, ids.size, idp,
+                           None if st is None else C.byref(st))
+    if rc != OK:
+        raise CfxError(rc, lib.cfx_last_error(None).decode())
+
+
+class Idm:
+    """One cfx_idm: B starts x E stimulation trains that share the identified parameters of every start
+    (``trains``: the arrays of ``cfx_idm_trains``, SoA with the train as the minor index).  Host numpy arrays are
+    checked, copied and the call returns when the results are back; with a CUDA ``theta`` every array must be a CUDA
+    tensor: used in place, unchecked, on torch's current stream."""
+
+    def __init__(self, *, model_id, constants: dict, scheme, n_steps, batch, n_trains, max_pulses, max_shooting,
+                 device=0):
+        self.lib = load_library()
+        cst = Constants()
+        for name, _ in Constants._fields_:
+            setattr(cst, name, float(constants.get(name, 0.0)))
+        h = C.c_void_p()
+        rc = self.lib.cfx_idm_create(model_id, C.byref(cst), scheme, n_steps, batch, n_trains, max_pulses,
+                                     max_shooting, device, C.byref(h))
+        if rc != OK:
+            raise CfxError(rc, self.lib.cfx_last_error(None).decode())
+        self.h = h
+        self.model_id, self.batch, self.n_trains = model_id, batch, n_trains
+        self.max_pulses, self.max_shooting, self.device = max_pulses, max_shooting, device
+        self.needs_value = model_id >= MODEL_IDS["ding2007"]
+
+    def _begin(self, trains, param_ids, theta):
+        """(struct, kept arrays, ids, id pointer, theta, new(shape), stream, flags) of one call."""
+        ids, idp = _idm_ids(param_ids)
+        B = self.batch
+        on_device = _is_tensor(theta)
+        st, keep = _idm_trains(trains, self.n_trains, self.max_pulses, self.max_shooting, self.needs_value,
+                               self.device if on_device else None)
+        if on_device:
+            import torch
+
+            dev = f"cuda:{self.device}"
+            if not (theta.is_cuda and theta.dtype == torch.float64 and theta.is_contiguous()
+                    and tuple(theta.shape) == (ids.size, B)):
+                raise CfxError(EINVAL, f"idm: theta must be a contiguous float64 ({ids.size}, {B}) tensor on {dev}")
+            new = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)  # noqa: E731
+            stream, fl = torch.cuda.current_stream().cuda_stream, DEVICE
+        else:
+            theta = np.ascontiguousarray(theta, dtype=np.float64)
+            if theta.shape != (ids.size, B):
+                raise CfxError(EINVAL, f"idm: theta must have shape ({ids.size}, {B}), not {theta.shape}")
+            new = lambda *sh: np.empty(sh)  # noqa: E731
+            stream, fl = None, 0
+        return st, keep, ids, idp, theta, new, stream, fl
+
+    def _check(self, rc):
+        if rc != OK:
+            raise CfxError(rc, self.lib.cfx_idm_last_error(self.h).decode())
+
+    def forces(self, trains: dict, param_ids, theta, with_sens=False):
+        """cfx_idm_forces: node forces (E, max_shooting + 1, B) and, with ``with_sens``, dF / dtheta
+        (E, max_shooting + 1, n_id, B); NaN past a train's own n_shooting.  Returns (force, sens or None)."""
+        st, keep, ids, idp, theta, new, stream, fl = self._begin(trains, param_ids, theta)
+        E, nn, B = self.n_trains, self.max_shooting + 1, self.batch
+        force = new(E, nn, B)
+        sens = new(E, nn, ids.size, B) if with_sens else None
+        self._check(self.lib.cfx_idm_forces(self.h, C.byref(st), ids.size, idp, _ptr(theta), _ptr(force), _ptr(sens),
+                                            fl, stream))
+        return force, sens
+
+    def normal(self, trains: dict, param_ids, theta, per_train=False, out=None):
+        """cfx_idm_normal: cost (B,), grad (n_id, B), the packed Gauss-Newton lower triangle (n_id (n_id + 1) / 2, B)
+        summed over the trains in train order and, with ``per_train``, cost_per_train (E, B) (else None).  ``out``:
+        (cost, grad, gn, cost_per_train or None) buffers to write into."""
+        st, keep, ids, idp, theta, new, stream, fl = self._begin(trains, param_ids, theta)
+        n, B = ids.size, self.batch
+        if out is None:
+            out = (new(B), new(n, B), new(n * (n + 1) // 2, B), new(self.n_trains, B) if per_train else None)
+        cost, grad, gn, cpt = out
+        self._check(self.lib.cfx_idm_normal(self.h, C.byref(st), n, idp, _ptr(theta), _ptr(cost), _ptr(grad),
+                                            _ptr(gn), _ptr(cpt), fl, stream))
+        return cost, grad, gn, cpt
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.cfx_idm_destroy(self.h)
             self.h = None
 
     def __del__(self):

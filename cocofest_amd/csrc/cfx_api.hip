@@ -15,6 +15,7 @@
 #include "cfx_colloc_ivp.h"
 #include "cfx_ident.h"
 #include "cfx_identf.h"
+#include "cfx_idm.h"
 #include "cfx_internal.h"
 #include "cfx_launch.h"
 #include "cfx_msk_launch.h"
@@ -2559,3 +2560,320 @@ extern "C" int cfx_gather_sum(int64_t batch, int64_t n_dst, const int32_t* ptr, 
     }
     return CFX_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------
+// multi-train force-parameter identification (cfx_idm.h): E trains share the parameters of every start
+// ------------------------------------------------------------------------------------------------------
+struct cfx_idm {
+    int model = 0, scheme = 1, device = 0;
+    int64_t B = 0;
+    int32_t E = 0, P = 0, Nmax = 0, m = 1;
+    bool needs_value = false;
+    IdmParams ip{};
+    hipStream_t stream = nullptr;
+    double* d_ws = nullptr;  // [E][1 + 8 + 36][B]: the per-train normal equations (host and device calls)
+    // staging of host calls: times, value, final_time, target, weight, theta, force, sens, cost | grad | gn | cost_per_train
+    DevBuf dbuf[9];
+    int32_t* d_int = nullptr;  // act [P][E] + the three counts [E]
+    std::string err;
+};
+
+static const int kIdmRowsMax = 1 + CFX_ID_MAX_PARAMS + CFX_ID_MAX_PARAMS * (CFX_ID_MAX_PARAMS + 1) / 2;
+
+// Every argument check of cfx_idm_create (ids == nullptr: no parameter list), cfx_idm_forces and cfx_idm_normal;
+// tr != nullptr: the host arrays too.  The train rules are cfx_sweep_check's with the train in the instance's place.
+static int idm_check(const char* fn, int model, int scheme, int n_steps, int64_t B, int E, int P, int Nmax,
+                     bool with_ids, int32_t n_id, const int32_t* ids, int32_t* col, const cfx_idm_trains* tr,
+                     std::string& msg) {
+    const std::string f = std::string(fn) + ": ";
+    if (model < CFX_DING2003 || model > CFX_HMED2018_FATIGUE) return msg = f + "unknown model", CFX_EINVAL;
+    if (is_fatigue(model))
+        return msg = f + "identification is not available for the fatigue models", CFX_EUNSUPPORTED;
+    if (E < 1) return msg = f + "n_trains must be positive", CFX_EINVAL;
+    if (E > kMaxGridY) return msg = f + "n_trains must be <= 65535", CFX_EINVAL;
+    if (with_ids) {
+        std::string m2;
+        const int rc = id_check(model, n_id, ids, col, m2);
+        if (rc != CFX_OK) return msg = std::string(fn) + m2.substr(6), rc;  // "cfx_id" -> the caller's name
+    }
+    cfx_sweep_trains st{};
+    if (tr) {
+        st.times = tr->times;
+        st.act_node = tr->act_node;
+        st.value = tr->value;
+        st.n_pulses = tr->n_pulses;
+        st.truncation = tr->truncation;
+        st.n_shooting = tr->n_shooting;
+        st.final_time = tr->final_time;
+    }
+    // batch first (the sweep's "batch" below is the train count)
+    if (B < 1) return msg = f + "n_steps, batch, max_pulses and max_shooting must be positive", CFX_EINVAL;
+    int rc = sweep_check(fn, model, scheme, n_steps, E, P, Nmax, tr ? &st : nullptr, msg);
+    if (rc != CFX_OK) {
+        const size_t at = msg.find(": instance ");
+        if (at != std::string::npos) msg.replace(at + 2, 8, "train");
+        return rc;
+    }
+    if (!tr) return CFX_OK;
+    for (int pass = 0; pass < 2; ++pass) {
+        const double* a = pass == 0 ? tr->target : tr->weight;
+        if (!a) continue;
+        for (int e = 0; e < E; ++e)
+            for (int k = 0; k <= tr->n_shooting[e]; ++k) {
+                const double v = a[(int64_t)k * E + e];
+                if (!std::isfinite(v) || (pass == 1 && v < 0.0))
+                    return msg = f + "train " + std::to_string(e) + ": node " + std::to_string(k) +
+                                 (pass == 0 ? ": target is not finite" : ": weight must be finite and >= 0"),
+                           CFX_EINVAL;
+            }
+    }
+    return CFX_OK;
+}
+
+extern "C" int cfx_idm_check(int32_t model, int32_t scheme, int32_t n_steps, int64_t batch, int32_t n_trains,
+                             int32_t max_pulses, int32_t max_shooting, int32_t n_id, const int32_t* param_ids,
+                             const cfx_idm_trains* trains) {
+    int32_t col[ID_SLOTS];
+    return idm_check("cfx_idm_check", model, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, true, n_id,
+                     param_ids, col, trains, g_create_error);
+}
+
+extern "C" void cfx_idm_destroy(cfx_idm* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    if (s->stream) (void)hipStreamSynchronize(s->stream);
+    for (DevBuf& b : s->dbuf)
+        if (b.p) (void)hipFree(b.p);
+    if (s->d_int) (void)hipFree(s->d_int);
+    if (s->d_ws) (void)hipFree(s->d_ws);
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    delete s;
+}
+
+extern "C" const char* cfx_idm_last_error(const cfx_idm* s) { return s ? s->err.c_str() : g_create_error.c_str(); }
+
+extern "C" int cfx_idm_create(int32_t model, const cfx_constants* c, int32_t scheme, int32_t n_steps, int64_t batch,
+                              int32_t n_trains, int32_t max_pulses, int32_t max_shooting, int32_t device,
+                              cfx_idm** out) {
+    if (!c || !out) return g_create_error = "cfx_idm_create: NULL argument", CFX_EINVAL;
+    *out = nullptr;
+    int rc = idm_check("cfx_idm_create", model, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, false, 0,
+                       nullptr, nullptr, nullptr, g_create_error);
+    if (rc != CFX_OK) return rc;
+    if (!(c->tauc > 0.0)) return g_create_error = "cfx_idm_create: tauc must be positive", CFX_EINVAL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return g_create_error = "cfx_idm_create: no HIP device available (libcfx has no CPU path)", CFX_ENODEV;
+    if (device < 0 || device >= ndev) return g_create_error = "cfx_idm_create: bad device ordinal", CFX_ENODEV;
+    cfx_idm* s = new cfx_idm();
+    s->model = model;
+    s->scheme = scheme;
+    s->device = device;
+    s->B = batch;
+    s->E = n_trains;
+    s->P = max_pulses;
+    s->Nmax = max_shooting;
+    s->m = n_steps;
+    s->needs_value = is_pw(model) || is_int(model);
+    IdmParams& ip = s->ip;
+    ip.B = batch;
+    ip.E = n_trains;
+    ip.P = max_pulses;
+    ip.Nmax = max_shooting;
+    ip.m = n_steps;
+    ip.inv_tauc = 1.0 / c->tauc;
+    ip.mult = c->fl * c->fv + c->fp;
+    ip.r0_km = c->r0_km_relationship;
+    for (int k = 0; k < ID_SLOTS; ++k) ip.def[k] = 0.0;
+    ip.def[ID_A] = is_pw(model) ? c->a_scale : c->a_rest;
+    ip.def[ID_KM] = c->km_rest;
+    ip.def[ID_TAU1] = c->tau1_rest;
+    ip.def[ID_TAU2] = c->tau2;
+    if (is_pw(model)) {
+        ip.def[ID_P4] = c->pd0;
+        ip.def[ID_P5] = c->pdt;
+    }
+    if (is_int(model)) {
+        ip.def[ID_P4] = c->ar;
+        ip.def[ID_P5] = c->bs;
+        ip.def[ID_P6] = c->Is;
+        ip.def[ID_P7] = c->cr;
+    }
+    if (hipSetDevice(device) != hipSuccess ||
+        hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
+        s->stream = nullptr;
+        cfx_idm_destroy(s);
+        return g_create_error = "cfx_idm_create: could not create a stream on the device", CFX_EHIP;
+    }
+    if (hipMalloc((void**)&s->d_ws, (size_t)n_trains * kIdmRowsMax * (size_t)batch * sizeof(double)) != hipSuccess) {
+        s->d_ws = nullptr;
+        cfx_idm_destroy(s);
+        return g_create_error = "cfx_idm_create: hipMalloc of the workspace failed", CFX_ENOMEM;
+    }
+    *out = s;
+    return CFX_OK;
+}
+
+static int idm_fail(cfx_idm* s, int code, const std::string& msg) {
+    s->err = msg;
+    return code;
+}
+
+// device buffer `slot` of at least n doubles
+static double* idm_buf(cfx_idm* s, int slot, size_t n, int* rc) {
+    DevBuf& b = s->dbuf[slot];
+    if (b.n < n) {
+        if (b.p) (void)hipFree(b.p);
+        b.p = nullptr;
+        b.n = 0;
+        if (hipMalloc(&b.p, n * sizeof(double)) != hipSuccess) {
+            b.p = nullptr;
+            *rc = idm_fail(s, CFX_ENOMEM, "cfx_idm: hipMalloc failed");
+            return nullptr;
+        }
+        b.n = n;
+    }
+    return b.p;
+}
+
+#define IDM_HIP(call)                                                                                          \
+    do {                                                                                                       \
+        hipError_t e_ = (call);                                                                                \
+        if (e_ != hipSuccess) return idm_fail(s, CFX_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// What both calls do before the launch: the argument checks, and for a host call the upload of the trains and of
+// theta.  Fills ip (trains, columns) and *TH, the device theta; *st the stream to launch on.
+static int idm_begin(cfx_idm* s, const char* fn, const cfx_idm_trains* tr, bool normal, int32_t n_id,
+                     const int32_t* ids, const double* theta, uint32_t flags, void* hip_stream, IdmParams& ip,
+                     const double** TH, hipStream_t* st) {
+    const std::string f = std::string(fn) + ": ";
+    if (!tr || !theta) return idm_fail(s, CFX_EINVAL, f + "trains or theta is NULL");
+    if (!tr->times || !tr->act_node || !tr->n_pulses || !tr->truncation || !tr->n_shooting || !tr->final_time ||
+        (s->needs_value && !tr->value))
+        return idm_fail(s, CFX_EINVAL, f + "a train array is NULL");
+    if (normal && (!tr->target || !tr->weight)) return idm_fail(s, CFX_EINVAL, f + "target or weight is NULL");
+    const bool dev = (flags & CFX_DEVICE) != 0;
+    int32_t col[ID_SLOTS];
+    // with device arrays only the creation arguments and the parameter list can be checked here
+    int rc = idm_check(fn, s->model, s->scheme, s->m, s->B, s->E, s->P, s->Nmax, true, n_id, ids, col,
+                       dev ? nullptr : tr, s->err);
+    if (rc != CFX_OK) return rc;
+    if (hipSetDevice(s->device) != hipSuccess) return idm_fail(s, CFX_EHIP, f + "hipSetDevice failed");
+    ip = s->ip;
+    ip.n_id = n_id;
+    for (int k = 0; k < ID_SLOTS; ++k) ip.col[k] = col[k];
+    if (dev) {
+        ip.times = tr->times;
+        ip.act = tr->act_node;
+        ip.value = tr->value;
+        ip.n_pulses = tr->n_pulses;
+        ip.truncation = tr->truncation;
+        ip.n_shooting = tr->n_shooting;
+        ip.final_time = tr->final_time;
+        ip.target = tr->target;
+        ip.weight = tr->weight;
+        *TH = theta;
+        *st = (hipStream_t)hip_stream;
+        return CFX_OK;
+    }
+    const size_t B = (size_t)s->B, E = (size_t)s->E, P = (size_t)s->P, nn = (size_t)s->Nmax + 1;
+    for (size_t i = 0; i < (size_t)n_id * B; ++i)
+        if (!std::isfinite(theta[i])) return idm_fail(s, CFX_EINVAL, f + "theta is not finite");
+    double* d_t = idm_buf(s, 0, P * E, &rc);
+    double* d_v = s->needs_value ? idm_buf(s, 1, P * E, &rc) : nullptr;
+    double* d_tf = idm_buf(s, 2, E, &rc);
+    double* d_y = normal ? idm_buf(s, 3, nn * E, &rc) : nullptr;
+    double* d_w = normal ? idm_buf(s, 4, nn * E, &rc) : nullptr;
+    double* d_th = idm_buf(s, 5, (size_t)CFX_ID_MAX_PARAMS * B, &rc);
+    if (!d_t || (s->needs_value && !d_v) || !d_tf || (normal && (!d_y || !d_w)) || !d_th) return rc;
+    if (!s->d_int && hipMalloc(&s->d_int, (P + 3) * E * sizeof(int32_t)) != hipSuccess) {
+        s->d_int = nullptr;
+        return idm_fail(s, CFX_ENOMEM, f + "hipMalloc failed");
+    }
+    int32_t* d_act = s->d_int;
+    int32_t* d_cnt = s->d_int + P * E;
+    hipStream_t q = s->stream;
+    IDM_HIP(hipMemcpyAsync(d_t, tr->times, P * E * sizeof(double), hipMemcpyHostToDevice, q));
+    if (d_v) IDM_HIP(hipMemcpyAsync(d_v, tr->value, P * E * sizeof(double), hipMemcpyHostToDevice, q));
+    IDM_HIP(hipMemcpyAsync(d_tf, tr->final_time, E * sizeof(double), hipMemcpyHostToDevice, q));
+    if (d_y) IDM_HIP(hipMemcpyAsync(d_y, tr->target, nn * E * sizeof(double), hipMemcpyHostToDevice, q));
+    if (d_w) IDM_HIP(hipMemcpyAsync(d_w, tr->weight, nn * E * sizeof(double), hipMemcpyHostToDevice, q));
+    IDM_HIP(hipMemcpyAsync(d_th, theta, (size_t)n_id * B * sizeof(double), hipMemcpyHostToDevice, q));
+    IDM_HIP(hipMemcpyAsync(d_act, tr->act_node, P * E * sizeof(int32_t), hipMemcpyHostToDevice, q));
+    IDM_HIP(hipMemcpyAsync(d_cnt, tr->n_pulses, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
+    IDM_HIP(hipMemcpyAsync(d_cnt + E, tr->truncation, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
+    IDM_HIP(hipMemcpyAsync(d_cnt + 2 * E, tr->n_shooting, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
+    ip.times = d_t;
+    ip.act = d_act;
+    ip.value = d_v;
+    ip.n_pulses = d_cnt;
+    ip.truncation = d_cnt + E;
+    ip.n_shooting = d_cnt + 2 * E;
+    ip.final_time = d_tf;
+    ip.target = d_y;
+    ip.weight = d_w;
+    *TH = d_th;
+    *st = q;
+    return CFX_OK;
+}
+
+// slots 0..3 only: the 4-direction kernels
+static int idm_dirs(const IdmParams& ip) {
+    for (int k = 4; k < ID_SLOTS; ++k)
+        if (ip.col[k] >= 0) return 8;
+    return 4;
+}
+
+extern "C" int cfx_idm_forces(cfx_idm* s, const cfx_idm_trains* tr, int32_t n_id, const int32_t* param_ids,
+                              const double* theta, double* force, double* sens, uint32_t flags, void* hip_stream) {
+    if (!s) return g_create_error = "cfx_idm_forces: NULL handle", CFX_EINVAL;
+    if (!force) return idm_fail(s, CFX_EINVAL, "cfx_idm_forces: force is NULL");
+    IdmParams ip;
+    const double* TH = nullptr;
+    hipStream_t st = nullptr;
+    int rc = idm_begin(s, "cfx_idm_forces", tr, false, n_id, param_ids, theta, flags, hip_stream, ip, &TH, &st);
+    if (rc != CFX_OK) return rc;
+    const size_t nf = (size_t)s->E * ((size_t)s->Nmax + 1) * (size_t)s->B, ns = nf * (size_t)n_id;
+    if (flags & CFX_DEVICE) {
+        IDM_HIP(launch_idm_sens(s->model, s->scheme, idm_dirs(ip), ip, TH, force, sens, st));
+        return CFX_OK;
+    }
+    double* d_f = idm_buf(s, 6, nf, &rc);
+    double* d_s = sens ? idm_buf(s, 7, ns, &rc) : nullptr;
+    if (!d_f || (sens && !d_s)) return rc;
+    IDM_HIP(launch_idm_sens(s->model, s->scheme, idm_dirs(ip), ip, TH, d_f, d_s, st));
+    IDM_HIP(hipMemcpyAsync(force, d_f, nf * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (d_s) IDM_HIP(hipMemcpyAsync(sens, d_s, ns * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipStreamSynchronize(st));
+    return CFX_OK;
+}
+
+extern "C" int cfx_idm_normal(cfx_idm* s, const cfx_idm_trains* tr, int32_t n_id, const int32_t* param_ids,
+                              const double* theta, double* cost, double* grad, double* gn, double* cost_per_train,
+                              uint32_t flags, void* hip_stream) {
+    if (!s) return g_create_error = "cfx_idm_normal: NULL handle", CFX_EINVAL;
+    if (!cost || !grad || !gn) return idm_fail(s, CFX_EINVAL, "cfx_idm_normal: cost, grad or gn is NULL");
+    IdmParams ip;
+    const double* TH = nullptr;
+    hipStream_t st = nullptr;
+    int rc = idm_begin(s, "cfx_idm_normal", tr, true, n_id, param_ids, theta, flags, hip_stream, ip, &TH, &st);
+    if (rc != CFX_OK) return rc;
+    const int d = idm_dirs(ip);
+    if (flags & CFX_DEVICE) {
+        IDM_HIP(launch_idm_normal(s->model, s->scheme, d, ip, TH, s->d_ws, cost, grad, gn, cost_per_train, st));
+        return CFX_OK;
+    }
+    const size_t B = (size_t)s->B, n = (size_t)n_id, npk = n * (n + 1) / 2, E = (size_t)s->E;
+    double* d_o = idm_buf(s, 8, (1 + n + npk + E) * B, &rc);
+    if (!d_o) return rc;
+    double *d_c = d_o, *d_g = d_o + B, *d_h = d_g + n * B, *d_p = cost_per_train ? d_h + npk * B : nullptr;
+    IDM_HIP(launch_idm_normal(s->model, s->scheme, d, ip, TH, s->d_ws, d_c, d_g, d_h, d_p, st));
+    IDM_HIP(hipMemcpyAsync(cost, d_c, B * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipMemcpyAsync(grad, d_g, n * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipMemcpyAsync(gn, d_h, npk * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (d_p) IDM_HIP(hipMemcpyAsync(cost_per_train, d_p, E * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipStreamSynchronize(st));
+    return CFX_OK;
+}
+#undef IDM_HIP

@@ -8,6 +8,10 @@ iteration is ONE ``cfx_id_normal`` launch (cost, gradient and Gauss-Newton matri
 each), followed by batched torch operations on the device for the tiny n_id x n_id damped solves, the gain ratio
 and the damping update.  Models: Ding2003, Ding2007 and Hmed2018 without fatigue.
 
+``FesMultiTrainIdentification`` fits ONE parameter set to several recordings at once (the reference's ``data_path``
+lists: trains at different frequencies, pulse widths or intensities), ``min_theta sum_e dt_e sum_k w_ek (F_ek - y_ek)^2``:
+every iteration is one ``cfx_idm_normal`` launch over all starts and all trains.
+
 ``FesFatigueIdentification`` is step 2 of the published protocol: with the force parameters fixed (the model's own
 values), the four fatigue parameters alpha_a, alpha_tau1, alpha_km, tau_fat of a ``*WithFatigue`` model are fitted to
 a fatiguing train the same way, one ``cfx_idf_normal`` launch per iteration.
@@ -21,7 +25,7 @@ import numpy as np
 
 from . import _cfx
 from .fes_models import DingModelPulseIntensityFrequency, DingModelPulseWidthFrequency, FesModel
-from .ivp import IvpFes
+from .ivp import PLACEHOLDER_TIME, IvpFes, pack_train, sweep_order
 from .ode_solver import OdeSolver
 
 # Default initial guesses and bounds of the identified parameters: the reference's ``_set_default_values`` tables
@@ -351,3 +355,247 @@ class FesFatigueIdentification(_MultistartIdentification):
         defaults = {k: (own[k], *sorted((0.01 * own[k], 100.0 * own[k]))) for k in FATIGUE_KEYS}
         self._setup(model, defaults, stim_time, final_time, force_tracking, key_parameter_to_identify, pulse_width,
                     pulse_intensity, ode_solver, bounds, initial_guess, n_starts, seed, start_spread, weight, device)
+
+
+def force_at_node(time, force, n_shooting, final_time):
+    """A recorded force curve (samples ``time``, ``force``) at the n_shooting + 1 nodes of [0, final_time], by linear
+    interpolation (the reference's ``force_at_node_in_ocp``, identification_method.py:253-278)."""
+    return [float(v) for v in np.interp(np.linspace(0, final_time, n_shooting + 1), time, force)]
+
+
+class FesMultiTrainIdentification(_MultistartIdentification):
+    """Force-parameter identification of one muscle from SEVERAL measured force curves, each under its own
+    stimulation train, over ``n_starts`` starts: one parameter set for all trains (the reference's ``data_path``
+    list of recordings).
+
+    ``trains``: a list of dicts, one per recording:
+      * ``stim_time``, ``final_time``; ``pulse_width`` (Ding2007) or ``pulse_intensity`` (Hmed2018):
+        ``{"fixed": value or one value per pulse}``;
+      * ``force_tracking``: the measured force at every node of that train's own ``OcpFes.prepare_n_shooting``,
+        or recorded samples ``time`` and ``force`` (interpolated onto the nodes by ``force_at_node``);
+      * optional ``weight`` (per node, default 1), ``pulse_mode`` (default "single"), ``sum_stim_truncation``
+        (default the model's; no upper limit).
+    Every train starts from the rest state.  Every other argument, ``starts``, ``forces``, ``solve`` and ``close``
+    are as ``FesIdentification``; ``forces`` returns one array per train, and ``solve`` adds ``"cost_per_train"``
+    (the best start's) and ``starts["cost_per_train"]`` (n_starts, n_trains)."""
+
+    def __init__(self, model=None, trains=None, key_parameter_to_identify=None,
+                 ode_solver=OdeSolver.RK4(n_integration_steps=10), bounds=None, initial_guess=None, n_starts=64,
+                 seed=0, start_spread=0.5, device=0):
+        if not isinstance(model, FesModel):
+            raise TypeError("model must be a FesModel type")
+        if model._with_fatigue:
+            raise ValueError("The given model is not valid and should not be including the fatigue equation in the "
+                             "model")
+        if not isinstance(trains, list) or not trains or not all(isinstance(t, dict) for t in trains):
+            raise TypeError("trains must be a non-empty list of dict")
+        self.family = _family(model)
+        defaults = DEFAULT_VALUES[self.family]
+        if not isinstance(key_parameter_to_identify, list):
+            raise TypeError(f"The given key_parameter_to_identify must be list type,"
+                            f" the given value is {type(key_parameter_to_identify)} type")
+        for key in key_parameter_to_identify:
+            if key not in defaults:
+                raise ValueError(f"The given key_parameter_to_identify is not valid,"
+                                 f" the given value is {key},"
+                                 f" the available values are {list(defaults.keys())}")
+        if len(set(key_parameter_to_identify)) != len(key_parameter_to_identify) or not key_parameter_to_identify:
+            raise ValueError("key_parameter_to_identify must list every parameter once, and at least one")
+        if not isinstance(ode_solver, (OdeSolver.RK1, OdeSolver.RK2, OdeSolver.RK4)):
+            raise TypeError("ode_solver must be a OdeSolver.RK1, RK2 or RK4 type")
+        if isinstance(n_starts, bool) or not isinstance(n_starts, int) or n_starts < 1:
+            raise ValueError("n_starts must be a positive int")
+        self.model = copy.deepcopy(model)  # the caller's model is left as it is
+        self.ode_solver = ode_solver
+        self.keys = list(key_parameter_to_identify)
+        self.param_ids = [self._PARAM_IDS[k] for k in self.keys]
+        self.n_starts, self.seed, self.start_spread, self.device = n_starts, seed, float(start_spread), device
+        self._ivps, packed, self.targets, self.weights = [], [], [], []
+        for e, train in enumerate(trains):
+            try:
+                ivp, target, weight = self._train(train)
+                packed.append(pack_train(ivp))
+            except (TypeError, ValueError) as err:
+                raise type(err)(f"trains[{e}]: {err}") from None
+            self._ivps.append(ivp)
+            self.targets.append(target)
+            self.weights.append(weight)
+        self.n_trains = len(trains)
+        self.n_shooting = [t["n_shooting"] for t in packed]
+        self.final_time = [t["final_time"] for t in packed]
+        m = ode_solver.n_integration_steps
+        # launch order: heaviest train first (a block is one train); results are returned in the caller's order
+        self.order = sweep_order([t["n_shooting"] * m * max(1, min(t["truncation"], len(t["times"]))) for t in packed])
+        self.max_pulses = max(1, max(len(t["times"]) for t in packed))
+        self.max_shooting = max(self.n_shooting)
+        self.trains = self._pack([packed[i] for i in self.order])
+        bounds, initial_guess = bounds or {}, initial_guess or {}
+        for key in list(bounds) + list(initial_guess):
+            if key not in self.keys:
+                raise ValueError(f"bounds / initial_guess given for {key}, which is not identified")
+        self.lower = np.array([bounds.get(k, defaults[k][1:])[0] for k in self.keys], dtype=np.float64)
+        self.upper = np.array([bounds.get(k, defaults[k][1:])[1] for k in self.keys], dtype=np.float64)
+        guess = np.array([initial_guess.get(k, defaults[k][0]) for k in self.keys], dtype=np.float64)
+        self.initial_guess = np.clip(guess, self.lower, self.upper)
+        # every argument check of libcfx, before any handle (and device) exists
+        _cfx.idm_check(self.model.cfx_model_id, ode_solver.scheme, m, n_starts, self.n_trains, self.max_pulses,
+                       self.max_shooting, self.param_ids, self.trains)
+        self._handles, self._dev_trains = {}, {}
+
+    def _train(self, train):
+        """(IvpFes, target, weight) of one train, with FesIdentification's checks and messages."""
+        unknown = set(train) - {"stim_time", "final_time", "force_tracking", "time", "force", "pulse_width",
+                                "pulse_intensity", "weight", "pulse_mode", "sum_stim_truncation"}
+        if unknown:
+            raise ValueError(f"unknown keys {sorted(unknown)}")
+        final_time = train.get("final_time")
+        if isinstance(final_time, bool) or not isinstance(final_time, int | float):
+            raise TypeError("final_time must be int or float type.")
+        if not train.get("stim_time"):
+            raise ValueError("stim_time must be given, here or in the model")
+        model = copy.deepcopy(self.model)
+        model.stim_time = list(train["stim_time"])
+        if any(t != PLACEHOLDER_TIME for t in model.previous_stim["time"]):
+            raise ValueError("previous_stim is not supported: every train starts from the rest state")
+        model.previous_stim = {k: [] for k in model.previous_stim}
+        if train.get("sum_stim_truncation") is not None:
+            T = train["sum_stim_truncation"]
+            if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+                raise ValueError("sum_stim_truncation must be a positive int")
+            model._sum_stim_truncation = T
+        fes = {"model": model, "pulse_mode": train.get("pulse_mode", "single")}
+        if self.family == "ding2007":
+            pulse_width = train.get("pulse_width")
+            if not isinstance(pulse_width, dict):
+                raise TypeError(f"pulse_width must be dict type, currently pulse_width is {type(pulse_width)}) type.")
+            if "fixed" not in pulse_width:
+                raise ValueError("pulse_width must hold the key 'fixed' (a value, or one value per pulse)")
+            fes["pulse_width"] = pulse_width["fixed"]
+        if self.family == "hmed2018":
+            pulse_intensity = train.get("pulse_intensity")
+            if not isinstance(pulse_intensity, dict):
+                raise TypeError(f"pulse_intensity must be dict type,"
+                                f" currently pulse_intensity is {type(pulse_intensity)}) type.")
+            if "fixed" not in pulse_intensity:
+                raise ValueError("pulse_intensity must hold the key 'fixed' (a value, or one value per pulse)")
+            if isinstance(pulse_intensity["fixed"], bool) or not isinstance(pulse_intensity["fixed"],
+                                                                              int | float | list):
+                raise ValueError("fixed pulse_intensity must be a int, float or list type.")
+            fes["pulse_intensity"] = pulse_intensity["fixed"]
+        ivp = IvpFes(fes, {"final_time": final_time, "ode_solver": self.ode_solver})
+        force_tracking = train.get("force_tracking")
+        if force_tracking is None and "time" in train and "force" in train:
+            force_tracking = force_at_node(train["time"], train["force"], ivp.n_shooting, final_time)
+        if not isinstance(force_tracking, list):
+            raise TypeError(f"force_tracking must be list type,"
+                            f" currently force_tracking is {type(force_tracking)}) type.")
+        if not all(isinstance(val, int | float) for val in force_tracking):
+            raise TypeError("force_tracking must be list of int or float type.")
+        if len(force_tracking) != ivp.n_shooting + 1:
+            raise ValueError(f"force_tracking has {len(force_tracking)} values, expected one per node: n_shooting + 1 "
+                             f"= {ivp.n_shooting + 1}")
+        target = np.asarray(force_tracking, dtype=np.float64)
+        weight = np.ones(ivp.n_shooting + 1) if train.get("weight") is None else np.asarray(train["weight"],
+                                                                                            dtype=np.float64)
+        if weight.shape != target.shape:
+            raise ValueError("weight must hold one value per node")
+        return ivp, target, weight
+
+    def _pack(self, packed) -> dict:
+        """SoA arrays of ``cfx_idm_trains`` in launch order (``packed``: ``pack_train`` dicts, already ordered)."""
+        E, P, nn = len(packed), self.max_pulses, self.max_shooting + 1
+        with_value = packed[0]["value"] is not None
+        out = {"times": np.zeros((P, E)), "act_node": np.zeros((P, E), dtype=np.int32),
+               "value": np.zeros((P, E)) if with_value else None,
+               "n_pulses": np.array([len(t["times"]) for t in packed], dtype=np.int32),
+               "truncation": np.array([t["truncation"] for t in packed], dtype=np.int32),
+               "n_shooting": np.array([t["n_shooting"] for t in packed], dtype=np.int32),
+               "final_time": np.array([t["final_time"] for t in packed], dtype=np.float64),
+               "target": np.zeros((nn, E)), "weight": np.zeros((nn, E))}
+        for j, t in enumerate(packed):
+            n, e = len(t["times"]), int(self.order[j])
+            out["times"][:n, j] = t["times"]
+            out["act_node"][:n, j] = t["act_node"]
+            if with_value:
+                out["value"][:n, j] = t["value"]
+            out["target"][: t["n_shooting"] + 1, j] = self.targets[e]
+            out["weight"][: t["n_shooting"] + 1, j] = self.weights[e]
+        return out
+
+    def _handle(self, batch):
+        if batch not in self._handles:
+            self._handles[batch] = _cfx.Idm(
+                model_id=self.model.cfx_model_id, constants=self.model.cfx_constants(), scheme=self.ode_solver.scheme,
+                n_steps=self.ode_solver.n_integration_steps, batch=batch, n_trains=self.n_trains,
+                max_pulses=self.max_pulses, max_shooting=self.max_shooting, device=self.device)
+        return self._handles[batch]
+
+    def _device_trains(self, dev):
+        """The packed trains on ``dev``, uploaded once per device."""
+        import torch
+
+        key = str(torch.device(dev))
+        if key not in self._dev_trains:
+            self._dev_trains[key] = {k: (None if v is None else torch.as_tensor(v, device=dev))
+                                     for k, v in self.trains.items()}
+        return self._dev_trains[key]
+
+    # ---- evaluation -----------------------------------------------------------------------------------
+    def forces(self, theta, with_sensitivities=False):
+        """Per train, in the caller's order: node forces (N_e + 1, B) for parameters theta (n_id, B)
+        (cfx_idm_forces); with ``with_sensitivities`` also the list of dF_k / dtheta_j (N_e + 1, n_id, B).  numpy in,
+        numpy out; CUDA tensors in, CUDA tensors out."""
+        if _cfx._is_tensor(theta):
+            B, trains = theta.shape[1], self._device_trains(theta.device)
+        else:
+            theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(len(self.keys), -1)
+            B, trains = theta.shape[1], self.trains
+        force, sens = self._handle(B).forces(trains, self.param_ids, theta, with_sens=with_sensitivities)
+        inverse = np.argsort(self.order)
+        F = [force[int(inverse[e]), : self.n_shooting[e] + 1] for e in range(self.n_trains)]
+        if not with_sensitivities:
+            return F
+        return F, [sens[int(inverse[e]), : self.n_shooting[e] + 1] for e in range(self.n_trains)]
+
+    def solve(self, max_iter=100, gtol=1e-8, xtol=1e-10):
+        """Levenberg-Marquardt from every start (``lm_solve``) on the joint cost.  Returns what
+        ``FesIdentification.solve`` returns, plus "cost_per_train" (n_trains,), the best start's, and
+        ``starts["cost_per_train"]`` (n_starts, n_trains), both in the caller's order of the trains."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        idm = self._handle(self.n_starts)
+        n, B = len(self.keys), self.n_starts
+        on = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)  # noqa: E731
+        with torch.cuda.device(dev):
+            trains = self._device_trains(dev)
+            new = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)  # noqa: E731
+            out = (new(B), new(n, B), new(n * (n + 1) // 2, B), None)
+
+            def normal(theta):
+                return idm.normal(trains, self.param_ids, theta.contiguous(), out=out)[:3]
+
+            theta, c, iters, status, hist = lm_solve(
+                normal, on(self.starts()), on(np.repeat(self.lower[:, None], B, 1)),
+                on(np.repeat(self.upper[:, None], B, 1)), max_iter=max_iter, gtol=gtol, xtol=xtol)
+            cpt = idm.normal(trains, self.param_ids, theta.contiguous(), per_train=True)[3]
+            theta, c, iters, status, hist, cpt = (t.cpu().numpy() for t in (theta, c, iters, status, hist, cpt))
+        cpt = cpt[np.argsort(self.order)].T.copy()  # (n_starts, n_trains), caller's order
+        ok = np.where(np.isfinite(c), c, np.inf)
+        best = int(np.argmin(ok))
+        result = dict(self.model.identifiable_parameters)
+        for j, key in enumerate(self.keys):
+            result[key] = float(theta[j, best])
+        result["cost"] = float(c[best])
+        result["cost_per_train"] = cpt[best].copy()
+        result["best_start"] = best
+        result["starts"] = {"theta": theta.T.copy(), "cost": c, "iterations": iters, "status": status,
+                            "cost_history": hist, "cost_per_train": cpt}
+        return result
+
+    def close(self):
+        for h in getattr(self, "_handles", {}).values():
+            h.close()
+        self._handles, self._dev_trains = {}, {}
+        for ivp in getattr(self, "_ivps", []):
+            ivp.close()

@@ -673,6 +673,50 @@ int cfx_sweep_integrate(cfx_sweep *s, const cfx_sweep_trains *trains, const doub
 const char *cfx_sweep_last_error(const cfx_sweep *s);
 void cfx_sweep_destroy(cfx_sweep *s);
 
+/* ---- multi-train force-parameter identification (one parameter set, several recordings) ---------------
+   The joint fit of the reference's *ForceParameterIdentification classes over a list of recordings:
+     min_theta sum_e dt_e sum_k w_{e,k} (F_{e,k}(theta) - y_{e,k})^2,   dt_e = final_time_e / n_shooting_e,
+   over E trains that share theta [n_id][B] (B starts; per-instance constants as cfx_id_*, param_ids CFX_P_*, 1..8,
+   distinct, valid for the model) and each start from the rest state.  Ding2003, Ding2007, Hmed2018; a fatigue model:
+   CFX_EUNSUPPORTED.  Every train has its own pulses, truncation (no upper bound: the calcium forcing and its
+   tangents are formed on the device), n_shooting, final_time, widths / intensities, target and weights.  All trains
+   of all starts go through one launch (plus the sum over the trains, in train order, no atomics).
+   cfx_idm_trains: the fields of cfx_sweep_trains with the TRAIN as the minor index (times, act_node, value [P][E];
+   n_pulses, truncation, n_shooting, final_time [E]; same rules), plus target and weight [max_shooting + 1][E]
+   (cfx_idm_normal only; entries past a train's own n_shooting are not read).
+   cfx_idm_forces: force [E][max_shooting + 1][B] and (sens != NULL) sens [E][max_shooting + 1][n_id][B]; NaN past a
+   train's own n_shooting.
+   cfx_idm_normal: cost [B], grad [n_id][B], gn [n_id (n_id + 1) / 2][B] in cfx_id_normal's packing, summed over the
+   trains in train order, and (cost_per_train != NULL) cost_per_train [E][B].
+   Host arrays are checked before the launch: a violation returns CFX_EINVAL, names the train and the pulse, and
+   launches nothing.  With CFX_DEVICE every pointer (the fields of trains, theta, the outputs) is a device pointer the
+   caller is responsible for; the call is asynchronous on `hip_stream` (NULL = the HIP null stream), copies nothing,
+   and uses the handle's workspace, so calls on one handle must be ordered.  param_ids is always a host array.
+   cfx_idm_check: every argument check without a device (trains == NULL: the creation arguments and the parameter
+   list only; target and weight are checked where they are given); message through cfx_last_error(NULL), as are
+   cfx_idm_create's. */
+typedef struct cfx_idm cfx_idm;
+typedef struct cfx_idm_trains {
+    const double *times;
+    const int32_t *act_node;
+    const double *value;
+    const int32_t *n_pulses, *truncation, *n_shooting;
+    const double *final_time;
+    const double *target, *weight;
+} cfx_idm_trains;
+int cfx_idm_create(int32_t model, const cfx_constants *constants, int32_t scheme, int32_t n_steps, int64_t batch,
+                   int32_t n_trains, int32_t max_pulses, int32_t max_shooting, int32_t device, cfx_idm **out);
+int cfx_idm_check(int32_t model, int32_t scheme, int32_t n_steps, int64_t batch, int32_t n_trains, int32_t max_pulses,
+                  int32_t max_shooting, int32_t n_id, const int32_t *param_ids, const cfx_idm_trains *trains);
+int cfx_idm_forces(cfx_idm *s, const cfx_idm_trains *trains, int32_t n_id, const int32_t *param_ids,
+                   const double *theta, double *force, double *sens /* may be NULL */, uint32_t flags,
+                   void *hip_stream);
+int cfx_idm_normal(cfx_idm *s, const cfx_idm_trains *trains, int32_t n_id, const int32_t *param_ids,
+                   const double *theta, double *cost, double *grad, double *gn,
+                   double *cost_per_train /* may be NULL */, uint32_t flags, void *hip_stream);
+const char *cfx_idm_last_error(const cfx_idm *s);
+void cfx_idm_destroy(cfx_idm *s);
+
 /* ---- placing gathered value slices --------------------------------------------------------------------
    dst[b][i] = sum over s in [ptr[i], ptr[i+1]) of src[b][idx[s]] for the batch-major (AoS) src [batch][src_len] and
    dst [batch][n_dst] on `hip_stream` (device pointers; ptr / idx device int32 arrays): the fixed gather table that
