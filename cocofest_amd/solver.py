@@ -1032,6 +1032,13 @@ class BatchedIpm:
         vfinal = full(x)
         g, f = self._eval_gf(vfinal)
         y = y * self.sg / self.sf[:, None]  # multipliers of the unscaled problem
+        # bound multipliers of the unscaled problem (grad f + J^T y - z_l + z_u = 0), 0 at the fixed variables: as
+        # NativeIpm.last_bound_multipliers
+        zs = self.sf[:, None] * self.d
+        z_full = torch.zeros((2, B, self.n), dtype=torch.float64, device=self.dev)
+        z_full[0][:, self.freeT] = zl / zs
+        z_full[1][:, self.freeT] = zu / zs
+        self.last_bound_multipliers = (z_full[0].cpu().numpy(), z_full[1].cpu().numpy())
         if self.dev.type == "cuda":
             torch.cuda.synchronize()
         return IpmResult(v=vfinal.cpu().numpy(), y=y.cpu().numpy(), f=f.cpu().numpy(),

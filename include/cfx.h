@@ -595,7 +595,8 @@ int cfx_ipm_create(cfx_handle *h, const double *lb, const double *ub, int32_t n_
 /* v0 [B][nv] starting points; fixed_values [B][n_fixed] values of the fixed variables in index order (NULL: their
    bound); outputs (any may be NULL): v [B][nv], y [B][ng] multipliers of the unscaled problem, f [B],
    converged [B], iterations [B], kkt_error [B] (scaled).  CFX_DEVICE: every pointer is a device pointer and the
-   outputs are written asynchronously on the handle's stream; otherwise host pointers. */
+   outputs are written asynchronously on the handle's stream; otherwise host pointers.  Sign convention of y and of
+   cfx_ipm_get_bound_multipliers' z_l, z_u: grad f + J^T y - z_l + z_u = 0 on the free variables, z_l, z_u >= 0. */
 int cfx_ipm_solve(cfx_ipm *s, const double *v0, const double *fixed_values, double *v, double *y, double *f,
                   int32_t *converged, int32_t *iterations, double *kkt_error, uint32_t flags);
 /* Ipopt's warm_start_init_point inputs (ABI 9) for the following cfx_ipm_solve calls with the option set: y [B][ng]
