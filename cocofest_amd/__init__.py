@@ -20,8 +20,8 @@ from .fes_models import (
     ModelMaker,
 )
 from .fourier import FourierSeries
-from .identification import (FesFatigueIdentification, FesIdentification, FesMultiTrainIdentification,
-                             force_at_node)
+from .identification import (FesFatigueIdentification, FesIdentification, FesMultiTrainFatigueIdentification,
+                             FesMultiTrainIdentification, force_at_node)
 from .ivp import IvpFes, IvpSweep
 from .msk import FesMskModel, FesMskOcp, OcpFesMsk
 from .nmpc import FesNmpc, NmpcFesMsk, NmpcResult
@@ -33,6 +33,6 @@ __all__ = [
     "CfxError", "Handle", "load_library", "DingModelFrequency", "DingModelFrequencyWithFatigue",
     "DingModelPulseIntensityFrequency", "DingModelPulseIntensityFrequencyWithFatigue",
     "DingModelPulseWidthFrequency", "DingModelPulseWidthFrequencyWithFatigue", "FesModel", "ModelMaker",
-    "FourierSeries", "FesIdentification", "FesFatigueIdentification", "FesMultiTrainIdentification", "force_at_node", "IvpFes", "IvpSweep", "FesOcp", "Axis", "Constraint", "ConstraintFcn", "ConstraintList", "Node", "Objective", "ObjectiveFcn", "ObjectiveList", "OcpFes",
+    "FourierSeries", "FesIdentification", "FesFatigueIdentification", "FesMultiTrainIdentification", "FesMultiTrainFatigueIdentification", "force_at_node", "IvpFes", "IvpSweep", "FesOcp", "Axis", "Constraint", "ConstraintFcn", "ConstraintList", "Node", "Objective", "ObjectiveFcn", "ObjectiveList", "OcpFes",
     "ControlType", "OdeSolver", "FesMskModel", "FesMskOcp", "OcpFesMsk", "FesNmpc", "NmpcFesMsk", "NmpcResult", "BatchedIpm", "IpmOptions", "IpmResult", "Solver",
 ]

@@ -253,6 +253,9 @@ SIGNATURES = {
     "cfx_idm_last_error": (C.c_char_p, [_P]),
     "cfx_idm_destroy": (None, [_P]),
 }
+# cfx_idfm_*: the signatures of cfx_idm_*
+SIGNATURES.update({name.replace("cfx_idm_", "cfx_idfm_"): sig for name, sig in list(SIGNATURES.items())
+                   if name.startswith("cfx_idm_")})
 
 _lib = None
 
@@ -1074,7 +1077,8 @@ def _idm_ids(param_ids):
     return ids, ids.ctypes.data_as(C.POINTER(C.c_int32))
 
 
-def idm_check(model_id, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, param_ids, trains: dict | None = None):
+def idm_check(model_id, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, param_ids, trains: dict | None = None,
+              prefix="cfx_idm"):
     """cfx_idm_check: the argument checks of ``Idm`` and of its host arrays, without a device.  Raises ``CfxError``
     with the library's message."""
     lib = load_library()
@@ -1082,10 +1086,17 @@ def idm_check(model_id, scheme, n_steps, batch, n_trains, max_pulses, max_shooti
     if trains is not None:
         st, _keep = _idm_trains(trains, n_trains, max_pulses, max_shooting, model_id >= MODEL_IDS["ding2007"])
     ids, idp = _idm_ids(param_ids)
-    rc = lib.cfx_idm_check(model_id, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, ids.size, idp,
-                           None if st is None else C.byref(st))
+    check = getattr(lib, prefix + "_check")
+    rc = check(model_id, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, ids.size, idp,
+               None if st is None else C.byref(st))
     if rc != OK:
         raise CfxError(rc, lib.cfx_last_error(None).decode())
+
+
+def idfm_check(model_id, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, param_ids, trains: dict | None = None):
+    """cfx_idfm_check: as ``idm_check`` for the fatigue models and ``FATIGUE_PARAM_IDS``."""
+    idm_check(model_id, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, param_ids, trains,
+              prefix="cfx_idfm")
 
 
 class Idm:
@@ -1094,6 +1105,11 @@ class Idm:
     checked, copied and the call returns when the results are back; with a CUDA ``theta`` every array must be a CUDA
     tensor: used in place, unchecked, on torch's current stream."""
 
+    _PREFIX = "cfx_idm"  # the entry points' family
+
+    def _fn(self, name):
+        return getattr(self.lib, f"{self._PREFIX}_{name}")
+
     def __init__(self, *, model_id, constants: dict, scheme, n_steps, batch, n_trains, max_pulses, max_shooting,
                  device=0):
         self.lib = load_library()
@@ -1101,8 +1117,8 @@ class Idm:
         for name, _ in Constants._fields_:
             setattr(cst, name, float(constants.get(name, 0.0)))
         h = C.c_void_p()
-        rc = self.lib.cfx_idm_create(model_id, C.byref(cst), scheme, n_steps, batch, n_trains, max_pulses,
-                                     max_shooting, device, C.byref(h))
+        rc = self._fn("create")(model_id, C.byref(cst), scheme, n_steps, batch, n_trains, max_pulses,
+                                max_shooting, device, C.byref(h))
         if rc != OK:
             raise CfxError(rc, self.lib.cfx_last_error(None).decode())
         self.h = h
@@ -1136,7 +1152,7 @@ class Idm:
 
     def _check(self, rc):
         if rc != OK:
-            raise CfxError(rc, self.lib.cfx_idm_last_error(self.h).decode())
+            raise CfxError(rc, self._fn("last_error")(self.h).decode())
 
     def forces(self, trains: dict, param_ids, theta, with_sens=False):
         """cfx_idm_forces: node forces (E, max_shooting + 1, B) and, with ``with_sens``, dF / dtheta
@@ -1145,8 +1161,8 @@ class Idm:
         E, nn, B = self.n_trains, self.max_shooting + 1, self.batch
         force = new(E, nn, B)
         sens = new(E, nn, ids.size, B) if with_sens else None
-        self._check(self.lib.cfx_idm_forces(self.h, C.byref(st), ids.size, idp, _ptr(theta), _ptr(force), _ptr(sens),
-                                            fl, stream))
+        self._check(self._fn("forces")(self.h, C.byref(st), ids.size, idp, _ptr(theta), _ptr(force), _ptr(sens),
+                                       fl, stream))
         return force, sens
 
     def normal(self, trains: dict, param_ids, theta, per_train=False, out=None):
@@ -1158,13 +1174,13 @@ class Idm:
         if out is None:
             out = (new(B), new(n, B), new(n * (n + 1) // 2, B), new(self.n_trains, B) if per_train else None)
         cost, grad, gn, cpt = out
-        self._check(self.lib.cfx_idm_normal(self.h, C.byref(st), n, idp, _ptr(theta), _ptr(cost), _ptr(grad),
-                                            _ptr(gn), _ptr(cpt), fl, stream))
+        self._check(self._fn("normal")(self.h, C.byref(st), n, idp, _ptr(theta), _ptr(cost), _ptr(grad),
+                                       _ptr(gn), _ptr(cpt), fl, stream))
         return cost, grad, gn, cpt
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.cfx_idm_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = None
 
     def __del__(self):
@@ -1172,3 +1188,10 @@ class Idm:
             self.close()
         except Exception:
             pass
+
+
+class Idfm(Idm):
+    """One cfx_idfm: ``Idm`` for a fatigue model, whose identified parameters are the fatigue parameters
+    (``FATIGUE_PARAM_IDS``); same arrays, same calls."""
+
+    _PREFIX = "cfx_idfm"

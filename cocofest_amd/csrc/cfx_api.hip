@@ -15,6 +15,7 @@
 #include "cfx_colloc_ivp.h"
 #include "cfx_ident.h"
 #include "cfx_identf.h"
+#include "cfx_idfm.h"
 #include "cfx_idm.h"
 #include "cfx_internal.h"
 #include "cfx_launch.h"
@@ -2580,6 +2581,9 @@ struct cfx_idm {
 
 static const int kIdmRowsMax = 1 + CFX_ID_MAX_PARAMS + CFX_ID_MAX_PARAMS * (CFX_ID_MAX_PARAMS + 1) / 2;
 
+static int idm_check_trains(const char* fn, int model, int scheme, int n_steps, int64_t B, int E, int P, int Nmax,
+                            const cfx_idm_trains* tr, std::string& msg);
+
 // Every argument check of cfx_idm_create (ids == nullptr: no parameter list), cfx_idm_forces and cfx_idm_normal;
 // tr != nullptr: the host arrays too.  The train rules are cfx_sweep_check's with the train in the instance's place.
 static int idm_check(const char* fn, int model, int scheme, int n_steps, int64_t B, int E, int P, int Nmax,
@@ -2596,6 +2600,14 @@ static int idm_check(const char* fn, int model, int scheme, int n_steps, int64_t
         const int rc = id_check(model, n_id, ids, col, m2);
         if (rc != CFX_OK) return msg = std::string(fn) + m2.substr(6), rc;  // "cfx_id" -> the caller's name
     }
+    return idm_check_trains(fn, model, scheme, n_steps, B, E, P, Nmax, tr, msg);
+}
+
+// The train rules (also cfx_idfm_*'s): cfx_sweep_check's with the train in the instance's place, then target and
+// weight.
+static int idm_check_trains(const char* fn, int model, int scheme, int n_steps, int64_t B, int E, int P, int Nmax,
+                            const cfx_idm_trains* tr, std::string& msg) {
+    const std::string f = std::string(fn) + ": ";
     cfx_sweep_trains st{};
     if (tr) {
         st.times = tr->times;
@@ -2742,6 +2754,14 @@ static double* idm_buf(cfx_idm* s, int slot, size_t n, int* rc) {
         if (e_ != hipSuccess) return idm_fail(s, CFX_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+struct IdmTrainPtrs {
+    const double *times, *value, *final_time, *target, *weight;
+    const int32_t *act, *n_pulses, *truncation, *n_shooting;
+};
+static int idm_stage(cfx_idm* s, const char* fn, const cfx_idm_trains* tr, bool normal, int32_t n_id,
+                     const double* theta, uint32_t flags, void* hip_stream, IdmTrainPtrs& tp, const double** TH,
+                     hipStream_t* st);
+
 // What both calls do before the launch: the argument checks, and for a host call the upload of the trains and of
 // theta.  Fills ip (trains, columns) and *TH, the device theta; *st the stream to launch on.
 static int idm_begin(cfx_idm* s, const char* fn, const cfx_idm_trains* tr, bool normal, int32_t n_id,
@@ -2759,20 +2779,41 @@ static int idm_begin(cfx_idm* s, const char* fn, const cfx_idm_trains* tr, bool 
     int rc = idm_check(fn, s->model, s->scheme, s->m, s->B, s->E, s->P, s->Nmax, true, n_id, ids, col,
                        dev ? nullptr : tr, s->err);
     if (rc != CFX_OK) return rc;
-    if (hipSetDevice(s->device) != hipSuccess) return idm_fail(s, CFX_EHIP, f + "hipSetDevice failed");
     ip = s->ip;
     ip.n_id = n_id;
     for (int k = 0; k < ID_SLOTS; ++k) ip.col[k] = col[k];
-    if (dev) {
-        ip.times = tr->times;
-        ip.act = tr->act_node;
-        ip.value = tr->value;
-        ip.n_pulses = tr->n_pulses;
-        ip.truncation = tr->truncation;
-        ip.n_shooting = tr->n_shooting;
-        ip.final_time = tr->final_time;
-        ip.target = tr->target;
-        ip.weight = tr->weight;
+    IdmTrainPtrs tp;
+    if ((rc = idm_stage(s, fn, tr, normal, n_id, theta, flags, hip_stream, tp, TH, st)) != CFX_OK) return rc;
+    ip.times = tp.times;
+    ip.act = tp.act;
+    ip.value = tp.value;
+    ip.n_pulses = tp.n_pulses;
+    ip.truncation = tp.truncation;
+    ip.n_shooting = tp.n_shooting;
+    ip.final_time = tp.final_time;
+    ip.target = tp.target;
+    ip.weight = tp.weight;
+    return CFX_OK;
+}
+
+// The device's view of the (checked) trains and of theta (also cfx_idfm_*'s): the caller's own pointers with
+// CFX_DEVICE, else the handle's staging buffers after the upload.  *st: the stream to launch on.
+static int idm_stage(cfx_idm* s, const char* fn, const cfx_idm_trains* tr, bool normal, int32_t n_id,
+                     const double* theta, uint32_t flags, void* hip_stream, IdmTrainPtrs& tp, const double** TH,
+                     hipStream_t* st) {
+    const std::string f = std::string(fn) + ": ";
+    int rc = CFX_OK;
+    if (hipSetDevice(s->device) != hipSuccess) return idm_fail(s, CFX_EHIP, f + "hipSetDevice failed");
+    if ((flags & CFX_DEVICE) != 0) {
+        tp.times = tr->times;
+        tp.act = tr->act_node;
+        tp.value = tr->value;
+        tp.n_pulses = tr->n_pulses;
+        tp.truncation = tr->truncation;
+        tp.n_shooting = tr->n_shooting;
+        tp.final_time = tr->final_time;
+        tp.target = tr->target;
+        tp.weight = tr->weight;
         *TH = theta;
         *st = (hipStream_t)hip_stream;
         return CFX_OK;
@@ -2804,15 +2845,15 @@ static int idm_begin(cfx_idm* s, const char* fn, const cfx_idm_trains* tr, bool 
     IDM_HIP(hipMemcpyAsync(d_cnt, tr->n_pulses, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
     IDM_HIP(hipMemcpyAsync(d_cnt + E, tr->truncation, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
     IDM_HIP(hipMemcpyAsync(d_cnt + 2 * E, tr->n_shooting, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    ip.times = d_t;
-    ip.act = d_act;
-    ip.value = d_v;
-    ip.n_pulses = d_cnt;
-    ip.truncation = d_cnt + E;
-    ip.n_shooting = d_cnt + 2 * E;
-    ip.final_time = d_tf;
-    ip.target = d_y;
-    ip.weight = d_w;
+    tp.times = d_t;
+    tp.act = d_act;
+    tp.value = d_v;
+    tp.n_pulses = d_cnt;
+    tp.truncation = d_cnt + E;
+    tp.n_shooting = d_cnt + 2 * E;
+    tp.final_time = d_tf;
+    tp.target = d_y;
+    tp.weight = d_w;
     *TH = d_th;
     *st = q;
     return CFX_OK;
@@ -2869,6 +2910,205 @@ extern "C" int cfx_idm_normal(cfx_idm* s, const cfx_idm_trains* tr, int32_t n_id
     if (!d_o) return rc;
     double *d_c = d_o, *d_g = d_o + B, *d_h = d_g + n * B, *d_p = cost_per_train ? d_h + npk * B : nullptr;
     IDM_HIP(launch_idm_normal(s->model, s->scheme, d, ip, TH, s->d_ws, d_c, d_g, d_h, d_p, st));
+    IDM_HIP(hipMemcpyAsync(cost, d_c, B * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipMemcpyAsync(grad, d_g, n * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipMemcpyAsync(gn, d_h, npk * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (d_p) IDM_HIP(hipMemcpyAsync(cost_per_train, d_p, E * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipStreamSynchronize(st));
+    return CFX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// multi-train fatigue-parameter identification (cfx_idfm.h): E trains share the fatigue parameters of every start.
+// The object is a cfx_idm (stream, workspace, staging buffers, error string) with the kernels' own constants.
+// ------------------------------------------------------------------------------------------------------
+struct cfx_idfm {
+    cfx_idm* core = nullptr;
+    IdfmParams fp{};
+};
+
+static const int kIdfmRowsMax = 1 + CFX_IDF_MAX_PARAMS + CFX_IDF_MAX_PARAMS * (CFX_IDF_MAX_PARAMS + 1) / 2;
+
+// Every argument check of cfx_idfm_create (no parameter list), cfx_idfm_forces and cfx_idfm_normal; tr != nullptr:
+// the host arrays too.  The train rules are cfx_idm_check's, the parameter-list rules cfx_idf_check's.
+static int idfm_check(const char* fn, int model, int scheme, int n_steps, int64_t B, int E, int P, int Nmax,
+                      bool with_ids, int32_t n_id, const int32_t* ids, int32_t* col, const cfx_idm_trains* tr,
+                      std::string& msg) {
+    const std::string f = std::string(fn) + ": ";
+    if (model < CFX_DING2003 || model > CFX_HMED2018_FATIGUE) return msg = f + "unknown model", CFX_EINVAL;
+    if (!is_fatigue(model))
+        return msg = f + "fatigue-parameter identification is only available for the fatigue models",
+               CFX_EUNSUPPORTED;
+    if (E < 1) return msg = f + "n_trains must be positive", CFX_EINVAL;
+    if (E > kMaxGridY) return msg = f + "n_trains must be <= 65535", CFX_EINVAL;
+    if (with_ids) {
+        std::string m2;
+        const int rc = idf_check(model, n_id, ids, col, m2);
+        if (rc != CFX_OK) return msg = std::string(fn) + m2.substr(7), rc;  // "cfx_idf" -> the caller's name
+    }
+    return idm_check_trains(fn, model, scheme, n_steps, B, E, P, Nmax, tr, msg);
+}
+
+extern "C" int cfx_idfm_check(int32_t model, int32_t scheme, int32_t n_steps, int64_t batch, int32_t n_trains,
+                              int32_t max_pulses, int32_t max_shooting, int32_t n_id, const int32_t* param_ids,
+                              const cfx_idm_trains* trains) {
+    int32_t col[IDF_SLOTS];
+    return idfm_check("cfx_idfm_check", model, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, true, n_id,
+                      param_ids, col, trains, g_create_error);
+}
+
+extern "C" void cfx_idfm_destroy(cfx_idfm* s) {
+    if (!s) return;
+    cfx_idm_destroy(s->core);
+    delete s;
+}
+
+extern "C" const char* cfx_idfm_last_error(const cfx_idfm* s) {
+    return s && s->core ? s->core->err.c_str() : g_create_error.c_str();
+}
+
+extern "C" int cfx_idfm_create(int32_t model, const cfx_constants* c, int32_t scheme, int32_t n_steps, int64_t batch,
+                               int32_t n_trains, int32_t max_pulses, int32_t max_shooting, int32_t device,
+                               cfx_idfm** out) {
+    if (!c || !out) return g_create_error = "cfx_idfm_create: NULL argument", CFX_EINVAL;
+    *out = nullptr;
+    int rc = idfm_check("cfx_idfm_create", model, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, false,
+                        0, nullptr, nullptr, nullptr, g_create_error);
+    if (rc != CFX_OK) return rc;
+    if (!(c->tauc > 0.0)) return g_create_error = "cfx_idfm_create: tauc must be positive", CFX_EINVAL;
+    if (!(c->tau_fat > 0.0)) return g_create_error = "cfx_idfm_create: tau_fat must be positive", CFX_EINVAL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return g_create_error = "cfx_idfm_create: no HIP device available (libcfx has no CPU path)", CFX_ENODEV;
+    if (device < 0 || device >= ndev) return g_create_error = "cfx_idfm_create: bad device ordinal", CFX_ENODEV;
+    cfx_idfm* s = new cfx_idfm();
+    cfx_idm* k = s->core = new cfx_idm();
+    k->model = model;
+    k->scheme = scheme;
+    k->device = device;
+    k->B = batch;
+    k->E = n_trains;
+    k->P = max_pulses;
+    k->Nmax = max_shooting;
+    k->m = n_steps;
+    k->needs_value = is_pw(model) || is_int(model);
+    IdfmParams& fp = s->fp;
+    fp.B = batch;
+    fp.E = n_trains;
+    fp.P = max_pulses;
+    fp.Nmax = max_shooting;
+    fp.m = n_steps;
+    fp.def[IDF_AA] = c->alpha_a;
+    fp.def[IDF_AT] = c->alpha_tau1;
+    fp.def[IDF_AK] = c->alpha_km;
+    fp.def[IDF_TF] = c->tau_fat;
+    fp.inv_tauc = 1.0 / c->tauc;
+    fp.mult = c->fl * c->fv + c->fp;
+    fp.r0m1 = c->km_rest + c->r0_km_relationship - 1.0;
+    fp.tau2 = c->tau2;
+    fp.a_rest = is_pw(model) ? c->a_scale : c->a_rest;  // ding2007_with_fatigue.py:198-241: A relaxes to a_scale
+    fp.tau1_rest = c->tau1_rest;
+    fp.km_rest = c->km_rest;
+    fp.pd0 = c->pd0;
+    fp.inv_pdt = is_pw(model) ? 1.0 / c->pdt : 0.0;
+    fp.ar = c->ar;
+    fp.bs = c->bs;
+    fp.Is = c->Is;
+    fp.cr = c->cr;
+    if (hipSetDevice(device) != hipSuccess ||
+        hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking) != hipSuccess) {
+        k->stream = nullptr;
+        cfx_idfm_destroy(s);
+        return g_create_error = "cfx_idfm_create: could not create a stream on the device", CFX_EHIP;
+    }
+    if (hipMalloc((void**)&k->d_ws, (size_t)n_trains * kIdfmRowsMax * (size_t)batch * sizeof(double)) != hipSuccess) {
+        k->d_ws = nullptr;
+        cfx_idfm_destroy(s);
+        return g_create_error = "cfx_idfm_create: hipMalloc of the workspace failed", CFX_ENOMEM;
+    }
+    *out = s;
+    return CFX_OK;
+}
+
+// idm_begin for the fatigue kernels: the argument checks, the upload of a host call, fp filled for the launch.
+static int idfm_begin(cfx_idfm* h, const char* fn, const cfx_idm_trains* tr, bool normal, int32_t n_id,
+                      const int32_t* ids, const double* theta, uint32_t flags, void* hip_stream, IdfmParams& fp,
+                      const double** TH, hipStream_t* st) {
+    cfx_idm* s = h->core;
+    const std::string f = std::string(fn) + ": ";
+    if (!tr || !theta) return idm_fail(s, CFX_EINVAL, f + "trains or theta is NULL");
+    if (!tr->times || !tr->act_node || !tr->n_pulses || !tr->truncation || !tr->n_shooting || !tr->final_time ||
+        (s->needs_value && !tr->value))
+        return idm_fail(s, CFX_EINVAL, f + "a train array is NULL");
+    if (normal && (!tr->target || !tr->weight)) return idm_fail(s, CFX_EINVAL, f + "target or weight is NULL");
+    const bool dev = (flags & CFX_DEVICE) != 0;
+    int32_t col[IDF_SLOTS];
+    // with device arrays only the creation arguments and the parameter list can be checked here
+    int rc = idfm_check(fn, s->model, s->scheme, s->m, s->B, s->E, s->P, s->Nmax, true, n_id, ids, col,
+                        dev ? nullptr : tr, s->err);
+    if (rc != CFX_OK) return rc;
+    fp = h->fp;
+    fp.n_id = n_id;
+    for (int k = 0; k < IDF_SLOTS; ++k) fp.col[k] = col[k];
+    IdmTrainPtrs tp;
+    if ((rc = idm_stage(s, fn, tr, normal, n_id, theta, flags, hip_stream, tp, TH, st)) != CFX_OK) return rc;
+    fp.times = tp.times;
+    fp.act = tp.act;
+    fp.value = tp.value;
+    fp.n_pulses = tp.n_pulses;
+    fp.truncation = tp.truncation;
+    fp.n_shooting = tp.n_shooting;
+    fp.final_time = tp.final_time;
+    fp.target = tp.target;
+    fp.weight = tp.weight;
+    return CFX_OK;
+}
+
+extern "C" int cfx_idfm_forces(cfx_idfm* h, const cfx_idm_trains* tr, int32_t n_id, const int32_t* param_ids,
+                               const double* theta, double* force, double* sens, uint32_t flags, void* hip_stream) {
+    if (!h) return g_create_error = "cfx_idfm_forces: NULL handle", CFX_EINVAL;
+    cfx_idm* s = h->core;
+    if (!force) return idm_fail(s, CFX_EINVAL, "cfx_idfm_forces: force is NULL");
+    IdfmParams fp;
+    const double* TH = nullptr;
+    hipStream_t st = nullptr;
+    int rc = idfm_begin(h, "cfx_idfm_forces", tr, false, n_id, param_ids, theta, flags, hip_stream, fp, &TH, &st);
+    if (rc != CFX_OK) return rc;
+    const size_t nf = (size_t)s->E * ((size_t)s->Nmax + 1) * (size_t)s->B, ns = nf * (size_t)n_id;
+    if (flags & CFX_DEVICE) {
+        IDM_HIP(launch_idfm_sens(s->model, s->scheme, fp, TH, force, sens, st));
+        return CFX_OK;
+    }
+    double* d_f = idm_buf(s, 6, nf, &rc);
+    double* d_s = sens ? idm_buf(s, 7, ns, &rc) : nullptr;
+    if (!d_f || (sens && !d_s)) return rc;
+    IDM_HIP(launch_idfm_sens(s->model, s->scheme, fp, TH, d_f, d_s, st));
+    IDM_HIP(hipMemcpyAsync(force, d_f, nf * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (d_s) IDM_HIP(hipMemcpyAsync(sens, d_s, ns * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipStreamSynchronize(st));
+    return CFX_OK;
+}
+
+extern "C" int cfx_idfm_normal(cfx_idfm* h, const cfx_idm_trains* tr, int32_t n_id, const int32_t* param_ids,
+                               const double* theta, double* cost, double* grad, double* gn, double* cost_per_train,
+                               uint32_t flags, void* hip_stream) {
+    if (!h) return g_create_error = "cfx_idfm_normal: NULL handle", CFX_EINVAL;
+    cfx_idm* s = h->core;
+    if (!cost || !grad || !gn) return idm_fail(s, CFX_EINVAL, "cfx_idfm_normal: cost, grad or gn is NULL");
+    IdfmParams fp;
+    const double* TH = nullptr;
+    hipStream_t st = nullptr;
+    int rc = idfm_begin(h, "cfx_idfm_normal", tr, true, n_id, param_ids, theta, flags, hip_stream, fp, &TH, &st);
+    if (rc != CFX_OK) return rc;
+    if (flags & CFX_DEVICE) {
+        IDM_HIP(launch_idfm_normal(s->model, s->scheme, fp, TH, s->d_ws, cost, grad, gn, cost_per_train, st));
+        return CFX_OK;
+    }
+    const size_t B = (size_t)s->B, n = (size_t)n_id, npk = n * (n + 1) / 2, E = (size_t)s->E;
+    double* d_o = idm_buf(s, 8, (1 + n + npk + E) * B, &rc);
+    if (!d_o) return rc;
+    double *d_c = d_o, *d_g = d_o + B, *d_h = d_g + n * B, *d_p = cost_per_train ? d_h + npk * B : nullptr;
+    IDM_HIP(launch_idfm_normal(s->model, s->scheme, fp, TH, s->d_ws, d_c, d_g, d_h, d_p, st));
     IDM_HIP(hipMemcpyAsync(cost, d_c, B * sizeof(double), hipMemcpyDeviceToHost, st));
     IDM_HIP(hipMemcpyAsync(grad, d_g, n * B * sizeof(double), hipMemcpyDeviceToHost, st));
     IDM_HIP(hipMemcpyAsync(gn, d_h, npk * B * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -346,5 +346,8 @@ hipError_t launch_idm_sens(int model, int scheme, int d, const IdmParams& P, con
                            double* sens, hipStream_t s);
 hipError_t launch_idm_normal(int model, int scheme, int d, const IdmParams& P, const double* theta, double* ws,
                              double* cost, double* grad, double* gn, double* cost_per_train, hipStream_t s);
+// The sum over the trains of a workspace WS [E][1 + n + n (n + 1) / 2][B], in train order (also cfx_idfm.h's).
+hipError_t launch_idm_reduce(int64_t B, int E, int n, const double* ws, double* cost, double* grad, double* gn,
+                             double* cost_per_train, hipStream_t s);
 
 }  // namespace cfx

@@ -86,9 +86,14 @@ hipError_t launch_idm_normal(int model, int scheme, int d, const IdmParams& P, c
                              double* cost, double* grad, double* gn, double* cost_per_train, hipStream_t s) {
     const hipError_t e = dispatch(model, scheme, d, P, NormalArgs{theta, ws}, s);
     if (e != hipSuccess) return e;
-    const int n = P.n_id, R = 1 + n + n * (n + 1) / 2;
-    hipLaunchKernelGGL(k_idm_reduce, dim3((unsigned)((P.B + 255) / 256), (unsigned)R), dim3(256), 0, s, P.B, P.E, R, n,
-                       ws, cost, grad, gn, cost_per_train);
+    return launch_idm_reduce(P.B, P.E, P.n_id, ws, cost, grad, gn, cost_per_train, s);
+}
+
+hipError_t launch_idm_reduce(int64_t B, int E, int n, const double* ws, double* cost, double* grad, double* gn,
+                             double* cost_per_train, hipStream_t s) {
+    const int R = 1 + n + n * (n + 1) / 2;
+    hipLaunchKernelGGL(k_idm_reduce, dim3((unsigned)((B + 255) / 256), (unsigned)R), dim3(256), 0, s, B, E, R, n, ws,
+                       cost, grad, gn, cost_per_train);
     return hipGetLastError();
 }
 

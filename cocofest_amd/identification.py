@@ -15,6 +15,8 @@ every iteration is one ``cfx_idm_normal`` launch over all starts and all trains.
 ``FesFatigueIdentification`` is step 2 of the published protocol: with the force parameters fixed (the model's own
 values), the four fatigue parameters alpha_a, alpha_tau1, alpha_km, tau_fat of a ``*WithFatigue`` model are fitted to
 a fatiguing train the same way, one ``cfx_idf_normal`` launch per iteration.
+``FesMultiTrainFatigueIdentification`` fits them jointly to several recordings (bursts, rest gaps of different
+lengths, test bursts: what determines tau_fat sharply), one ``cfx_idfm_normal`` launch per iteration.
 """
 
 from __future__ import annotations
@@ -363,34 +365,18 @@ def force_at_node(time, force, n_shooting, final_time):
     return [float(v) for v in np.interp(np.linspace(0, final_time, n_shooting + 1), time, force)]
 
 
-class FesMultiTrainIdentification(_MultistartIdentification):
-    """Force-parameter identification of one muscle from SEVERAL measured force curves, each under its own
-    stimulation train, over ``n_starts`` starts: one parameter set for all trains (the reference's ``data_path``
-    list of recordings).
+class _MultiTrainIdentification(_MultistartIdentification):
+    """What the two multi-train identification problems share: the per-train checks, packing in launch order, the
+    device copy of the trains, evaluation and the joint fit with its per-train results.  A subclass checks the model,
+    builds ``defaults`` {key: (guess, min, max)} and names its parameter ids, its libcfx object and its check."""
 
-    ``trains``: a list of dicts, one per recording:
-      * ``stim_time``, ``final_time``; ``pulse_width`` (Ding2007) or ``pulse_intensity`` (Hmed2018):
-        ``{"fixed": value or one value per pulse}``;
-      * ``force_tracking``: the measured force at every node of that train's own ``OcpFes.prepare_n_shooting``,
-        or recorded samples ``time`` and ``force`` (interpolated onto the nodes by ``force_at_node``);
-      * optional ``weight`` (per node, default 1), ``pulse_mode`` (default "single"), ``sum_stim_truncation``
-        (default the model's; no upper limit).
-    Every train starts from the rest state.  Every other argument, ``starts``, ``forces``, ``solve`` and ``close``
-    are as ``FesIdentification``; ``forces`` returns one array per train, and ``solve`` adds ``"cost_per_train"``
-    (the best start's) and ``starts["cost_per_train"]`` (n_starts, n_trains)."""
+    _HANDLE, _TRAIN_CHECK = _cfx.Idm, staticmethod(_cfx.idm_check)
 
-    def __init__(self, model=None, trains=None, key_parameter_to_identify=None,
-                 ode_solver=OdeSolver.RK4(n_integration_steps=10), bounds=None, initial_guess=None, n_starts=64,
-                 seed=0, start_spread=0.5, device=0):
-        if not isinstance(model, FesModel):
-            raise TypeError("model must be a FesModel type")
-        if model._with_fatigue:
-            raise ValueError("The given model is not valid and should not be including the fatigue equation in the "
-                             "model")
+    def _setup_trains(self, model, defaults, trains, key_parameter_to_identify, ode_solver, bounds, initial_guess,
+                      n_starts, seed, start_spread, device):
         if not isinstance(trains, list) or not trains or not all(isinstance(t, dict) for t in trains):
             raise TypeError("trains must be a non-empty list of dict")
         self.family = _family(model)
-        defaults = DEFAULT_VALUES[self.family]
         if not isinstance(key_parameter_to_identify, list):
             raise TypeError(f"The given key_parameter_to_identify must be list type,"
                             f" the given value is {type(key_parameter_to_identify)} type")
@@ -438,8 +424,8 @@ class FesMultiTrainIdentification(_MultistartIdentification):
         guess = np.array([initial_guess.get(k, defaults[k][0]) for k in self.keys], dtype=np.float64)
         self.initial_guess = np.clip(guess, self.lower, self.upper)
         # every argument check of libcfx, before any handle (and device) exists
-        _cfx.idm_check(self.model.cfx_model_id, ode_solver.scheme, m, n_starts, self.n_trains, self.max_pulses,
-                       self.max_shooting, self.param_ids, self.trains)
+        self._TRAIN_CHECK(self.model.cfx_model_id, ode_solver.scheme, m, n_starts, self.n_trains, self.max_pulses,
+                          self.max_shooting, self.param_ids, self.trains)
         self._handles, self._dev_trains = {}, {}
 
     def _train(self, train):
@@ -524,7 +510,7 @@ class FesMultiTrainIdentification(_MultistartIdentification):
 
     def _handle(self, batch):
         if batch not in self._handles:
-            self._handles[batch] = _cfx.Idm(
+            self._handles[batch] = self._HANDLE(
                 model_id=self.model.cfx_model_id, constants=self.model.cfx_constants(), scheme=self.ode_solver.scheme,
                 n_steps=self.ode_solver.n_integration_steps, batch=batch, n_trains=self.n_trains,
                 max_pulses=self.max_pulses, max_shooting=self.max_shooting, device=self.device)
@@ -599,3 +585,64 @@ class FesMultiTrainIdentification(_MultistartIdentification):
         self._handles, self._dev_trains = {}, {}
         for ivp in getattr(self, "_ivps", []):
             ivp.close()
+
+
+class FesMultiTrainIdentification(_MultiTrainIdentification):
+    """Force-parameter identification of one muscle from SEVERAL measured force curves, each under its own
+    stimulation train, over ``n_starts`` starts: one parameter set for all trains (the reference's ``data_path``
+    list of recordings).
+
+    ``trains``: a list of dicts, one per recording:
+      * ``stim_time``, ``final_time``; ``pulse_width`` (Ding2007) or ``pulse_intensity`` (Hmed2018):
+        ``{"fixed": value or one value per pulse}``;
+      * ``force_tracking``: the measured force at every node of that train's own ``OcpFes.prepare_n_shooting``,
+        or recorded samples ``time`` and ``force`` (interpolated onto the nodes by ``force_at_node``);
+      * optional ``weight`` (per node, default 1), ``pulse_mode`` (default "single"), ``sum_stim_truncation``
+        (default the model's; no upper limit).
+    Every train starts from the rest state.  Every other argument, ``starts``, ``forces``, ``solve`` and ``close``
+    are as ``FesIdentification``; ``forces`` returns one array per train, and ``solve`` adds ``"cost_per_train"``
+    (the best start's) and ``starts["cost_per_train"]`` (n_starts, n_trains)."""
+
+    def __init__(self, model=None, trains=None, key_parameter_to_identify=None,
+                 ode_solver=OdeSolver.RK4(n_integration_steps=10), bounds=None, initial_guess=None, n_starts=64,
+                 seed=0, start_spread=0.5, device=0):
+        if not isinstance(model, FesModel):
+            raise TypeError("model must be a FesModel type")
+        if model._with_fatigue:
+            raise ValueError("The given model is not valid and should not be including the fatigue equation in the "
+                             "model")
+        self._setup_trains(model, DEFAULT_VALUES[_family(model)], trains, key_parameter_to_identify, ode_solver,
+                           bounds, initial_guess, n_starts, seed, start_spread, device)
+
+
+class FesMultiTrainFatigueIdentification(_MultiTrainIdentification):
+    """Fatigue-parameter identification of one muscle from SEVERAL measured force curves: one set of alpha_a,
+    alpha_tau1, alpha_km, tau_fat for all recordings, the force parameters fixed at the model's own values.  This is
+    the fit for the recovery time constant: a short fatiguing train holds no recovery (tau_fat is not identifiable
+    from 1 s of data, and only loosely from a 5 s burst), a protocol of recordings with a fatiguing burst, rest gaps of
+    different lengths and a test burst determines it about 100 x more sharply.
+
+    ``model``: a ``*WithFatigue`` model; ``trains``: the list of dicts of ``FesMultiTrainIdentification`` (a
+    recording may hold thousands of nodes; ``sum_stim_truncation`` has no upper limit); keys, default initial guess
+    (the model's own value) and default bounds (0.01 x to 100 x that value, in increasing order) are those of
+    ``FesFatigueIdentification``.  ``starts``, ``forces`` (one array per train), ``solve`` (with ``"cost_per_train"``)
+    and ``close`` are as ``FesMultiTrainIdentification``; every iteration is one ``cfx_idfm_normal`` launch.
+
+    Every train starts from the fatigue rest state [0, 0, A_rest (Ding2007: a_scale), tau1_rest, km_rest].  A
+    recording that begins already fatigued is out of scope: its start state would depend on the parameters being
+    identified.  Put the rest gap and the test burst into the same recording as the fatiguing burst instead."""
+
+    _PARAM_IDS = _cfx.FATIGUE_PARAM_IDS
+    _HANDLE, _TRAIN_CHECK = _cfx.Idfm, staticmethod(_cfx.idfm_check)
+
+    def __init__(self, model=None, trains=None, key_parameter_to_identify=None,
+                 ode_solver=OdeSolver.RK4(n_integration_steps=10), bounds=None, initial_guess=None, n_starts=64,
+                 seed=0, start_spread=0.5, device=0):
+        if not isinstance(model, FesModel):
+            raise TypeError("model must be a FesModel type")
+        if not model._with_fatigue:
+            raise ValueError("The given model is not valid and should be including the fatigue equation in the model")
+        own = model.identifiable_parameters
+        defaults = {k: (own[k], *sorted((0.01 * own[k], 100.0 * own[k]))) for k in FATIGUE_KEYS}
+        self._setup_trains(model, defaults, trains, key_parameter_to_identify, ode_solver, bounds, initial_guess,
+                           n_starts, seed, start_spread, device)

@@ -11,7 +11,9 @@
  *   - the CasADi-generated NLP callbacks that Ipopt invokes on the OptimalControlProgram built at
  *     cocofest/optimization/fes_ocp.py:171-190 (Ipopt TNLP eval_f / eval_grad_f / eval_g /
  *     eval_jac_g / eval_h: solver-owned contiguous double arrays, COO sparsity fixed up front);
- *   - the single-shooting integration behind IvpFes.integrate (cocofest/integration/ivp_fes.py:282-297).
+ *   - the single-shooting integration behind IvpFes.integrate (cocofest/integration/ivp_fes.py:282-297);
+ *   - the parameter-identification OCPs (cocofest/identification): force parameters from one recording (cfx_id_*)
+ *     or several (cfx_idm_*), fatigue parameters from one recording (cfx_idf_*) or several (cfx_idfm_*).
  *
  * Conventions
  *   - Plain C types only.  Every buffer is caller-owned.  With CFX_DEVICE the pointers are HIP device
@@ -717,6 +719,32 @@ int cfx_idm_normal(cfx_idm *s, const cfx_idm_trains *trains, int32_t n_id, const
                    double *cost_per_train /* may be NULL */, uint32_t flags, void *hip_stream);
 const char *cfx_idm_last_error(const cfx_idm *s);
 void cfx_idm_destroy(cfx_idm *s);
+
+/* ---- multi-train fatigue-parameter identification (one fatigue-parameter set, several recordings) -----
+   cfx_idf_* over E recordings, with cfx_idm_*'s conventions: the same cost, the same cfx_idm_trains struct (array
+   shapes, rules, host checks that name the train and the pulse), the same output shapes, the optional
+   cost_per_train, and CFX_DEVICE semantics.  theta [n_id][B] holds per-start FATIGUE parameters: param_ids are
+   CFX_FP_*, 1..4, distinct; the force parameters are `constants`' own.  The *_WITH_FATIGUE models only; a model
+   without fatigue: CFX_EUNSUPPORTED.  Every train is shot from the fatigue rest state (0, 0, a_rest (Ding2007:
+   a_scale), tau1_rest, km_rest): a recording that begins already fatigued is out of scope (its start state would
+   depend on theta).  The calcium forcing is formed on the device, so the truncation has no upper bound and a
+   recording may hold thousands of nodes (max_shooting <= 65535): several recordings with rest gaps of different
+   lengths are what determines tau_fat sharply.  Messages of cfx_idfm_check and cfx_idfm_create through
+   cfx_last_error(NULL). */
+typedef struct cfx_idfm cfx_idfm;
+int cfx_idfm_create(int32_t model, const cfx_constants *constants, int32_t scheme, int32_t n_steps, int64_t batch,
+                    int32_t n_trains, int32_t max_pulses, int32_t max_shooting, int32_t device, cfx_idfm **out);
+int cfx_idfm_check(int32_t model, int32_t scheme, int32_t n_steps, int64_t batch, int32_t n_trains,
+                   int32_t max_pulses, int32_t max_shooting, int32_t n_id, const int32_t *param_ids,
+                   const cfx_idm_trains *trains);
+int cfx_idfm_forces(cfx_idfm *s, const cfx_idm_trains *trains, int32_t n_id, const int32_t *param_ids,
+                    const double *theta, double *force, double *sens /* may be NULL */, uint32_t flags,
+                    void *hip_stream);
+int cfx_idfm_normal(cfx_idfm *s, const cfx_idm_trains *trains, int32_t n_id, const int32_t *param_ids,
+                    const double *theta, double *cost, double *grad, double *gn,
+                    double *cost_per_train /* may be NULL */, uint32_t flags, void *hip_stream);
+const char *cfx_idfm_last_error(const cfx_idfm *s);
+void cfx_idfm_destroy(cfx_idfm *s);
 
 /* ---- placing gathered value slices --------------------------------------------------------------------
    dst[b][i] = sum over s in [ptr[i], ptr[i+1]) of src[b][idx[s]] for the batch-major (AoS) src [batch][src_len] and
