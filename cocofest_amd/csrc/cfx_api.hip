@@ -1383,9 +1383,12 @@ static int id_prepare(cfx_handle* h) {
     return CFX_OK;
 }
 
-// Everything both identification calls check before they touch the device.
-static int id_validate(cfx_handle* h, const char* fn, int32_t n_id, const int32_t* ids, const double* theta,
-                       const double* u, int64_t n_data, int32_t* col) {
+// Everything the single-train identification calls check before they touch the device.  check: the family's
+// parameter-list rules (id_check, idf_check), whose messages begin with a prefix of `strip` characters ("cfx_id",
+// "cfx_idf") that gives way to the caller's name.
+typedef int (*IdCheckFn)(int model, int32_t n_id, const int32_t* ids, int32_t* col, std::string& msg);
+static int id_validate(cfx_handle* h, const char* fn, IdCheckFn check, size_t strip, int32_t n_id, const int32_t* ids,
+                       const double* theta, const double* u, int64_t n_data, int32_t* col) {
     const std::string f(fn);
     if (h->msk) return fail(h, CFX_EUNSUPPORTED, f + ": not available for a musculoskeletal handle");
     if (h->colloc) return fail(h, CFX_EUNSUPPORTED, f + ": not available for a collocation transcription");
@@ -1393,8 +1396,8 @@ static int id_validate(cfx_handle* h, const char* fn, int32_t n_id, const int32_
     if (h->scheme != CFX_RK1 && h->scheme != CFX_RK2 && h->scheme != CFX_RK4)
         return fail(h, CFX_EUNSUPPORTED, f + ": the scheme must be CFX_RK1, CFX_RK2 or CFX_RK4");
     std::string msg;
-    const int rc = id_check(h->model, n_id, ids, col, msg);
-    if (rc != CFX_OK) return fail(h, rc, f + msg.substr(6));  // "cfx_id" -> the caller's name
+    const int rc = check(h->model, n_id, ids, col, msg);
+    if (rc != CFX_OK) return fail(h, rc, f + msg.substr(strip));
     if (!theta) return fail(h, CFX_EINVAL, f + ": theta is NULL");
     if (h->sz.nu > 0 && !u) return fail(h, CFX_EINVAL, f + ": this model needs the controls u");
     if (n_data != 1 && n_data != h->prob.batch)
@@ -1431,60 +1434,39 @@ static int id_dirs(const int32_t* col) {
     return 4;
 }
 
-extern "C" int cfx_id_forces(cfx_handle* h, int32_t n_id, const int32_t* param_ids, const double* theta,
-                             const double* u, int64_t n_data, double* force, double* sens, uint32_t flags) {
-    if (!h) {
-        g_create_error = "cfx_id_forces: NULL handle";
-        return CFX_EINVAL;
-    }
-    int32_t col[ID_SLOTS];
-    int rc = id_validate(h, "cfx_id_forces", n_id, param_ids, theta, u, n_data, col);
-    if (rc != CFX_OK) return rc;
-    if (!force) return fail(h, CFX_EINVAL, "cfx_id_forces: force is NULL");
-    CFX_HIP(h, hipSetDevice(h->device));
-    if ((rc = id_prepare(h)) != CFX_OK) return rc;
-    IdParams P = h->idp;
-    P.n_data = n_data;
-    P.n_id = n_id;
-    for (int s = 0; s < ID_SLOTS; ++s) P.col[s] = col[s];
-    const size_t B = (size_t)P.B, nn = (size_t)P.N + 1, nu = (size_t)h->sz.nu;
+// What cfx_id_forces and cfx_idf_forces do around their launch: the device's view of the inputs and outputs (the
+// caller's own arrays with CFX_DEVICE, else the handle's staging buffers), launch(TH, U, F, S) (a CFX_* code), the
+// copies back.
+template <class Launch>
+static int id_forces_staged(cfx_handle* h, int32_t n_id, const double* theta, const double* u, int64_t n_data,
+                            double* force, double* sens, uint32_t flags, Launch&& launch) {
+    int rc = CFX_OK;
+    const size_t B = (size_t)h->prob.batch, N = (size_t)h->prob.n_shooting, nn = N + 1, nu = (size_t)h->sz.nu;
     const double* TH = id_in(h, 0, theta, (size_t)n_id * B, flags, &rc);
     if (!TH) return rc;
-    const double* U = nu ? id_in(h, 1, u, (size_t)P.N * nu * (size_t)n_data, flags, &rc) : nullptr;
+    const double* U = nu ? id_in(h, 1, u, N * nu * (size_t)n_data, flags, &rc) : nullptr;
     if (nu && !U) return rc;
     double* F = id_out(h, 4, force, nn * B, flags, &rc);
     if (!F) return rc;
     double* S = sens ? id_out(h, 5, sens, nn * (size_t)n_id * B, flags, &rc) : nullptr;
     if (sens && !S) return rc;
-    CFX_HIP(h, launch_id_sens(h->model, h->scheme, id_dirs(col), P, TH, U, F, S, h->stream));
+    if ((rc = launch(TH, U, F, S)) != CFX_OK) return rc;
     if ((rc = id_back(h, F, force, nn * B, flags)) != CFX_OK) return rc;
     if (sens && (rc = id_back(h, S, sens, nn * (size_t)n_id * B, flags)) != CFX_OK) return rc;
     return sync_if_host(h, flags);
 }
 
-extern "C" int cfx_id_normal(cfx_handle* h, int32_t n_id, const int32_t* param_ids, const double* theta,
-                             const double* u, const double* target, const double* weight, int64_t n_data,
-                             double* cost, double* grad, double* gn, uint32_t flags) {
-    if (!h) {
-        g_create_error = "cfx_id_normal: NULL handle";
-        return CFX_EINVAL;
-    }
-    int32_t col[ID_SLOTS];
-    int rc = id_validate(h, "cfx_id_normal", n_id, param_ids, theta, u, n_data, col);
-    if (rc != CFX_OK) return rc;
-    if (!target || !weight) return fail(h, CFX_EINVAL, "cfx_id_normal: target or weight is NULL");
-    if (!cost || !grad || !gn) return fail(h, CFX_EINVAL, "cfx_id_normal: cost, grad or gn is NULL");
-    CFX_HIP(h, hipSetDevice(h->device));
-    if ((rc = id_prepare(h)) != CFX_OK) return rc;
-    IdParams P = h->idp;
-    P.n_data = n_data;
-    P.n_id = n_id;
-    for (int s = 0; s < ID_SLOTS; ++s) P.col[s] = col[s];
-    const size_t B = (size_t)P.B, nn = (size_t)P.N + 1, nu = (size_t)h->sz.nu, nd = (size_t)n_data;
-    const size_t npk = (size_t)n_id * (n_id + 1) / 2;
+// The same for cfx_id_normal and cfx_idf_normal: launch(TH, U, Y, W, C, G, H).
+template <class Launch>
+static int id_normal_staged(cfx_handle* h, int32_t n_id, const double* theta, const double* u, const double* target,
+                            const double* weight, int64_t n_data, double* cost, double* grad, double* gn,
+                            uint32_t flags, Launch&& launch) {
+    int rc = CFX_OK;
+    const size_t B = (size_t)h->prob.batch, N = (size_t)h->prob.n_shooting, nn = N + 1, nu = (size_t)h->sz.nu;
+    const size_t nd = (size_t)n_data, npk = (size_t)n_id * (n_id + 1) / 2;
     const double* TH = id_in(h, 0, theta, (size_t)n_id * B, flags, &rc);
     if (!TH) return rc;
-    const double* U = nu ? id_in(h, 1, u, (size_t)P.N * nu * nd, flags, &rc) : nullptr;
+    const double* U = nu ? id_in(h, 1, u, N * nu * nd, flags, &rc) : nullptr;
     if (nu && !U) return rc;
     const double* Y = id_in(h, 2, target, nn * nd, flags, &rc);
     if (!Y) return rc;
@@ -1496,11 +1478,62 @@ extern "C" int cfx_id_normal(cfx_handle* h, int32_t n_id, const int32_t* param_i
     if (!G) return rc;
     double* H = id_out(h, 8, gn, npk * B, flags, &rc);
     if (!H) return rc;
-    CFX_HIP(h, launch_id_normal(h->model, h->scheme, id_dirs(col), P, TH, U, Y, W, C, G, H, h->stream));
+    if ((rc = launch(TH, U, Y, W, C, G, H)) != CFX_OK) return rc;
     if ((rc = id_back(h, C, cost, B, flags)) != CFX_OK) return rc;
     if ((rc = id_back(h, G, grad, (size_t)n_id * B, flags)) != CFX_OK) return rc;
     if ((rc = id_back(h, H, gn, npk * B, flags)) != CFX_OK) return rc;
     return sync_if_host(h, flags);
+}
+
+extern "C" int cfx_id_forces(cfx_handle* h, int32_t n_id, const int32_t* param_ids, const double* theta,
+                             const double* u, int64_t n_data, double* force, double* sens, uint32_t flags) {
+    if (!h) {
+        g_create_error = "cfx_id_forces: NULL handle";
+        return CFX_EINVAL;
+    }
+    int32_t col[ID_SLOTS];
+    int rc = id_validate(h, "cfx_id_forces", id_check, 6, n_id, param_ids, theta, u, n_data, col);
+    if (rc != CFX_OK) return rc;
+    if (!force) return fail(h, CFX_EINVAL, "cfx_id_forces: force is NULL");
+    CFX_HIP(h, hipSetDevice(h->device));
+    if ((rc = id_prepare(h)) != CFX_OK) return rc;
+    IdParams P = h->idp;
+    P.n_data = n_data;
+    P.n_id = n_id;
+    for (int s = 0; s < ID_SLOTS; ++s) P.col[s] = col[s];
+    return id_forces_staged(h, n_id, theta, u, n_data, force, sens, flags,
+                            [&](const double* TH, const double* U, double* F, double* S) -> int {
+                                CFX_HIP(h, launch_id_sens(h->model, h->scheme, id_dirs(col), P, TH, U, F, S,
+                                                          h->stream));
+                                return CFX_OK;
+                            });
+}
+
+extern "C" int cfx_id_normal(cfx_handle* h, int32_t n_id, const int32_t* param_ids, const double* theta,
+                             const double* u, const double* target, const double* weight, int64_t n_data,
+                             double* cost, double* grad, double* gn, uint32_t flags) {
+    if (!h) {
+        g_create_error = "cfx_id_normal: NULL handle";
+        return CFX_EINVAL;
+    }
+    int32_t col[ID_SLOTS];
+    int rc = id_validate(h, "cfx_id_normal", id_check, 6, n_id, param_ids, theta, u, n_data, col);
+    if (rc != CFX_OK) return rc;
+    if (!target || !weight) return fail(h, CFX_EINVAL, "cfx_id_normal: target or weight is NULL");
+    if (!cost || !grad || !gn) return fail(h, CFX_EINVAL, "cfx_id_normal: cost, grad or gn is NULL");
+    CFX_HIP(h, hipSetDevice(h->device));
+    if ((rc = id_prepare(h)) != CFX_OK) return rc;
+    IdParams P = h->idp;
+    P.n_data = n_data;
+    P.n_id = n_id;
+    for (int s = 0; s < ID_SLOTS; ++s) P.col[s] = col[s];
+    return id_normal_staged(h, n_id, theta, u, target, weight, n_data, cost, grad, gn, flags,
+                            [&](const double* TH, const double* U, const double* Y, const double* W, double* C,
+                                double* G, double* H) -> int {
+                                CFX_HIP(h, launch_id_normal(h->model, h->scheme, id_dirs(col), P, TH, U, Y, W, C, G, H,
+                                                        h->stream));
+                                return CFX_OK;
+                            });
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1543,25 +1576,6 @@ static int idf_check(int model, int32_t n_id, const int32_t* ids, int32_t* col, 
 extern "C" int cfx_idf_check(int32_t model, int32_t n_id, const int32_t* param_ids) {
     int32_t col[IDF_SLOTS];
     return idf_check(model, n_id, param_ids, col, g_create_error);
-}
-
-// Everything both calls check before they touch the device (the order and the messages of id_validate).
-static int idf_validate(cfx_handle* h, const char* fn, int32_t n_id, const int32_t* ids, const double* theta,
-                        const double* u, int64_t n_data, int32_t* col) {
-    const std::string f(fn);
-    if (h->msk) return fail(h, CFX_EUNSUPPORTED, f + ": not available for a musculoskeletal handle");
-    if (h->colloc) return fail(h, CFX_EUNSUPPORTED, f + ": not available for a collocation transcription");
-    if (h->kp.tiled) return fail(h, CFX_EUNSUPPORTED, f + ": not available with CFX_LAYOUT_TILED64");
-    if (h->scheme != CFX_RK1 && h->scheme != CFX_RK2 && h->scheme != CFX_RK4)
-        return fail(h, CFX_EUNSUPPORTED, f + ": the scheme must be CFX_RK1, CFX_RK2 or CFX_RK4");
-    std::string msg;
-    const int rc = idf_check(h->model, n_id, ids, col, msg);
-    if (rc != CFX_OK) return fail(h, rc, f + msg.substr(7));  // "cfx_idf" -> the caller's name
-    if (!theta) return fail(h, CFX_EINVAL, f + ": theta is NULL");
-    if (h->sz.nu > 0 && !u) return fail(h, CFX_EINVAL, f + ": this model needs the controls u");
-    if (n_data != 1 && n_data != h->prob.batch)
-        return fail(h, CFX_EINVAL, f + ": n_data must be 1 or the batch size");
-    return CFX_OK;
 }
 
 // Kernel parameters of one call.  The stimulation tables are those of the force-parameter identification
@@ -1613,25 +1627,17 @@ extern "C" int cfx_idf_forces(cfx_handle* h, int32_t n_id, const int32_t* param_
         return CFX_EINVAL;
     }
     int32_t col[IDF_SLOTS];
-    int rc = idf_validate(h, "cfx_idf_forces", n_id, param_ids, theta, u, n_data, col);
+    int rc = id_validate(h, "cfx_idf_forces", idf_check, 7, n_id, param_ids, theta, u, n_data, col);
     if (rc != CFX_OK) return rc;
     if (!force) return fail(h, CFX_EINVAL, "cfx_idf_forces: force is NULL");
     CFX_HIP(h, hipSetDevice(h->device));
     IdfParams P;
     if ((rc = idf_params(h, n_id, col, n_data, P)) != CFX_OK) return rc;
-    const size_t B = (size_t)P.B, nn = (size_t)P.N + 1, nu = (size_t)h->sz.nu;
-    const double* TH = id_in(h, 0, theta, (size_t)n_id * B, flags, &rc);
-    if (!TH) return rc;
-    const double* U = nu ? id_in(h, 1, u, (size_t)P.N * nu * (size_t)n_data, flags, &rc) : nullptr;
-    if (nu && !U) return rc;
-    double* F = id_out(h, 4, force, nn * B, flags, &rc);
-    if (!F) return rc;
-    double* S = sens ? id_out(h, 5, sens, nn * (size_t)n_id * B, flags, &rc) : nullptr;
-    if (sens && !S) return rc;
-    CFX_HIP(h, launch_idf_sens(h->model, h->scheme, P, TH, U, F, S, h->stream));
-    if ((rc = id_back(h, F, force, nn * B, flags)) != CFX_OK) return rc;
-    if (sens && (rc = id_back(h, S, sens, nn * (size_t)n_id * B, flags)) != CFX_OK) return rc;
-    return sync_if_host(h, flags);
+    return id_forces_staged(h, n_id, theta, u, n_data, force, sens, flags,
+                            [&](const double* TH, const double* U, double* F, double* S) -> int {
+                                CFX_HIP(h, launch_idf_sens(h->model, h->scheme, P, TH, U, F, S, h->stream));
+                                return CFX_OK;
+                            });
 }
 
 extern "C" int cfx_idf_normal(cfx_handle* h, int32_t n_id, const int32_t* param_ids, const double* theta,
@@ -1642,34 +1648,19 @@ extern "C" int cfx_idf_normal(cfx_handle* h, int32_t n_id, const int32_t* param_
         return CFX_EINVAL;
     }
     int32_t col[IDF_SLOTS];
-    int rc = idf_validate(h, "cfx_idf_normal", n_id, param_ids, theta, u, n_data, col);
+    int rc = id_validate(h, "cfx_idf_normal", idf_check, 7, n_id, param_ids, theta, u, n_data, col);
     if (rc != CFX_OK) return rc;
     if (!target || !weight) return fail(h, CFX_EINVAL, "cfx_idf_normal: target or weight is NULL");
     if (!cost || !grad || !gn) return fail(h, CFX_EINVAL, "cfx_idf_normal: cost, grad or gn is NULL");
     CFX_HIP(h, hipSetDevice(h->device));
     IdfParams P;
     if ((rc = idf_params(h, n_id, col, n_data, P)) != CFX_OK) return rc;
-    const size_t B = (size_t)P.B, nn = (size_t)P.N + 1, nu = (size_t)h->sz.nu, nd = (size_t)n_data;
-    const size_t npk = (size_t)n_id * (n_id + 1) / 2;
-    const double* TH = id_in(h, 0, theta, (size_t)n_id * B, flags, &rc);
-    if (!TH) return rc;
-    const double* U = nu ? id_in(h, 1, u, (size_t)P.N * nu * nd, flags, &rc) : nullptr;
-    if (nu && !U) return rc;
-    const double* Y = id_in(h, 2, target, nn * nd, flags, &rc);
-    if (!Y) return rc;
-    const double* W = id_in(h, 3, weight, nn * nd, flags, &rc);
-    if (!W) return rc;
-    double* C = id_out(h, 6, cost, B, flags, &rc);
-    if (!C) return rc;
-    double* G = id_out(h, 7, grad, (size_t)n_id * B, flags, &rc);
-    if (!G) return rc;
-    double* H = id_out(h, 8, gn, npk * B, flags, &rc);
-    if (!H) return rc;
-    CFX_HIP(h, launch_idf_normal(h->model, h->scheme, P, TH, U, Y, W, C, G, H, h->stream));
-    if ((rc = id_back(h, C, cost, B, flags)) != CFX_OK) return rc;
-    if ((rc = id_back(h, G, grad, (size_t)n_id * B, flags)) != CFX_OK) return rc;
-    if ((rc = id_back(h, H, gn, npk * B, flags)) != CFX_OK) return rc;
-    return sync_if_host(h, flags);
+    return id_normal_staged(h, n_id, theta, u, target, weight, n_data, cost, grad, gn, flags,
+                            [&](const double* TH, const double* U, const double* Y, const double* W, double* C,
+                                double* G, double* H) -> int {
+                                CFX_HIP(h, launch_idf_normal(h->model, h->scheme, P, TH, U, Y, W, C, G, H, h->stream));
+                                return CFX_OK;
+                            });
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -2754,66 +2745,31 @@ static double* idm_buf(cfx_idm* s, int slot, size_t n, int* rc) {
         if (e_ != hipSuccess) return idm_fail(s, CFX_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-struct IdmTrainPtrs {
-    const double *times, *value, *final_time, *target, *weight;
-    const int32_t *act, *n_pulses, *truncation, *n_shooting;
-};
-static int idm_stage(cfx_idm* s, const char* fn, const cfx_idm_trains* tr, bool normal, int32_t n_id,
-                     const double* theta, uint32_t flags, void* hip_stream, IdmTrainPtrs& tp, const double** TH,
-                     hipStream_t* st);
+// The train rules and the parameter-list rules of a multi-train family: idm_check or idfm_check.
+typedef int (*IdmCheckFn)(const char* fn, int model, int scheme, int n_steps, int64_t B, int E, int P, int Nmax,
+                          bool with_ids, int32_t n_id, const int32_t* ids, int32_t* col, const cfx_idm_trains* tr,
+                          std::string& msg);
 
-// What both calls do before the launch: the argument checks, and for a host call the upload of the trains and of
-// theta.  Fills ip (trains, columns) and *TH, the device theta; *st the stream to launch on.
-static int idm_begin(cfx_idm* s, const char* fn, const cfx_idm_trains* tr, bool normal, int32_t n_id,
-                     const int32_t* ids, const double* theta, uint32_t flags, void* hip_stream, IdmParams& ip,
-                     const double** TH, hipStream_t* st) {
-    const std::string f = std::string(fn) + ": ";
-    if (!tr || !theta) return idm_fail(s, CFX_EINVAL, f + "trains or theta is NULL");
-    if (!tr->times || !tr->act_node || !tr->n_pulses || !tr->truncation || !tr->n_shooting || !tr->final_time ||
-        (s->needs_value && !tr->value))
-        return idm_fail(s, CFX_EINVAL, f + "a train array is NULL");
-    if (normal && (!tr->target || !tr->weight)) return idm_fail(s, CFX_EINVAL, f + "target or weight is NULL");
-    const bool dev = (flags & CFX_DEVICE) != 0;
-    int32_t col[ID_SLOTS];
-    // with device arrays only the creation arguments and the parameter list can be checked here
-    int rc = idm_check(fn, s->model, s->scheme, s->m, s->B, s->E, s->P, s->Nmax, true, n_id, ids, col,
-                       dev ? nullptr : tr, s->err);
-    if (rc != CFX_OK) return rc;
-    ip = s->ip;
-    ip.n_id = n_id;
-    for (int k = 0; k < ID_SLOTS; ++k) ip.col[k] = col[k];
-    IdmTrainPtrs tp;
-    if ((rc = idm_stage(s, fn, tr, normal, n_id, theta, flags, hip_stream, tp, TH, st)) != CFX_OK) return rc;
-    ip.times = tp.times;
-    ip.act = tp.act;
-    ip.value = tp.value;
-    ip.n_pulses = tp.n_pulses;
-    ip.truncation = tp.truncation;
-    ip.n_shooting = tp.n_shooting;
-    ip.final_time = tp.final_time;
-    ip.target = tp.target;
-    ip.weight = tp.weight;
-    return CFX_OK;
-}
-
-// The device's view of the (checked) trains and of theta (also cfx_idfm_*'s): the caller's own pointers with
-// CFX_DEVICE, else the handle's staging buffers after the upload.  *st: the stream to launch on.
+// The device's view of the (checked) trains and of theta, written into the kernel parameters ip (IdmParams or
+// IdfmParams: the same nine train pointers): the caller's own pointers with CFX_DEVICE, else the handle's staging
+// buffers after the upload.  *TH: the device theta; *st: the stream to launch on.
+template <class Params>
 static int idm_stage(cfx_idm* s, const char* fn, const cfx_idm_trains* tr, bool normal, int32_t n_id,
-                     const double* theta, uint32_t flags, void* hip_stream, IdmTrainPtrs& tp, const double** TH,
+                     const double* theta, uint32_t flags, void* hip_stream, Params& ip, const double** TH,
                      hipStream_t* st) {
     const std::string f = std::string(fn) + ": ";
     int rc = CFX_OK;
     if (hipSetDevice(s->device) != hipSuccess) return idm_fail(s, CFX_EHIP, f + "hipSetDevice failed");
     if ((flags & CFX_DEVICE) != 0) {
-        tp.times = tr->times;
-        tp.act = tr->act_node;
-        tp.value = tr->value;
-        tp.n_pulses = tr->n_pulses;
-        tp.truncation = tr->truncation;
-        tp.n_shooting = tr->n_shooting;
-        tp.final_time = tr->final_time;
-        tp.target = tr->target;
-        tp.weight = tr->weight;
+        ip.times = tr->times;
+        ip.act = tr->act_node;
+        ip.value = tr->value;
+        ip.n_pulses = tr->n_pulses;
+        ip.truncation = tr->truncation;
+        ip.n_shooting = tr->n_shooting;
+        ip.final_time = tr->final_time;
+        ip.target = tr->target;
+        ip.weight = tr->weight;
         *TH = theta;
         *st = (hipStream_t)hip_stream;
         return CFX_OK;
@@ -2845,17 +2801,80 @@ static int idm_stage(cfx_idm* s, const char* fn, const cfx_idm_trains* tr, bool 
     IDM_HIP(hipMemcpyAsync(d_cnt, tr->n_pulses, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
     IDM_HIP(hipMemcpyAsync(d_cnt + E, tr->truncation, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
     IDM_HIP(hipMemcpyAsync(d_cnt + 2 * E, tr->n_shooting, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    tp.times = d_t;
-    tp.act = d_act;
-    tp.value = d_v;
-    tp.n_pulses = d_cnt;
-    tp.truncation = d_cnt + E;
-    tp.n_shooting = d_cnt + 2 * E;
-    tp.final_time = d_tf;
-    tp.target = d_y;
-    tp.weight = d_w;
+    ip.times = d_t;
+    ip.act = d_act;
+    ip.value = d_v;
+    ip.n_pulses = d_cnt;
+    ip.truncation = d_cnt + E;
+    ip.n_shooting = d_cnt + 2 * E;
+    ip.final_time = d_tf;
+    ip.target = d_y;
+    ip.weight = d_w;
     *TH = d_th;
     *st = q;
+    return CFX_OK;
+}
+
+// What the forces and normal calls of both multi-train families do before the launch: the argument checks (check:
+// the family's rules), and for a host call the upload of the trains and of theta.  ip: the handle's parameters `base`
+// with this call's columns and trains; *TH the device theta; *st the stream to launch on.
+template <class Params>
+static int idm_begin(cfx_idm* s, const Params& base, IdmCheckFn check, const char* fn, const cfx_idm_trains* tr,
+                     bool normal, int32_t n_id, const int32_t* ids, const double* theta, uint32_t flags,
+                     void* hip_stream, Params& ip, const double** TH, hipStream_t* st) {
+    const std::string f = std::string(fn) + ": ";
+    if (!tr || !theta) return idm_fail(s, CFX_EINVAL, f + "trains or theta is NULL");
+    if (!tr->times || !tr->act_node || !tr->n_pulses || !tr->truncation || !tr->n_shooting || !tr->final_time ||
+        (s->needs_value && !tr->value))
+        return idm_fail(s, CFX_EINVAL, f + "a train array is NULL");
+    if (normal && (!tr->target || !tr->weight)) return idm_fail(s, CFX_EINVAL, f + "target or weight is NULL");
+    const bool dev = (flags & CFX_DEVICE) != 0;
+    constexpr int kSlots = (int)(sizeof(base.col) / sizeof(base.col[0]));
+    int32_t col[kSlots];
+    // with device arrays only the creation arguments and the parameter list can be checked here
+    const int rc = check(fn, s->model, s->scheme, s->m, s->B, s->E, s->P, s->Nmax, true, n_id, ids, col,
+                         dev ? nullptr : tr, s->err);
+    if (rc != CFX_OK) return rc;
+    ip = base;
+    ip.n_id = n_id;
+    for (int k = 0; k < kSlots; ++k) ip.col[k] = col[k];
+    return idm_stage(s, fn, tr, normal, n_id, theta, flags, hip_stream, ip, TH, st);
+}
+
+// What the forces calls of both families do around their launch: launch(F, S) (a CFX_* code) on the caller's arrays
+// with CFX_DEVICE, else on the handle's buffers, followed by the copies back and the synchronisation.
+template <class Launch>
+static int idm_forces_staged(cfx_idm* s, int32_t n_id, double* force, double* sens, uint32_t flags, hipStream_t st,
+                             Launch&& launch) {
+    int rc = CFX_OK;
+    if (flags & CFX_DEVICE) return launch(force, sens);
+    const size_t nf = (size_t)s->E * ((size_t)s->Nmax + 1) * (size_t)s->B, ns = nf * (size_t)n_id;
+    double* d_f = idm_buf(s, 6, nf, &rc);
+    double* d_s = sens ? idm_buf(s, 7, ns, &rc) : nullptr;
+    if (!d_f || (sens && !d_s)) return rc;
+    if ((rc = launch(d_f, d_s)) != CFX_OK) return rc;
+    IDM_HIP(hipMemcpyAsync(force, d_f, nf * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (d_s) IDM_HIP(hipMemcpyAsync(sens, d_s, ns * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipStreamSynchronize(st));
+    return CFX_OK;
+}
+
+// The same for the normal calls: launch(C, G, H, CPT).
+template <class Launch>
+static int idm_normal_staged(cfx_idm* s, int32_t n_id, double* cost, double* grad, double* gn, double* cost_per_train,
+                             uint32_t flags, hipStream_t st, Launch&& launch) {
+    int rc = CFX_OK;
+    if (flags & CFX_DEVICE) return launch(cost, grad, gn, cost_per_train);
+    const size_t B = (size_t)s->B, n = (size_t)n_id, npk = n * (n + 1) / 2, E = (size_t)s->E;
+    double* d_o = idm_buf(s, 8, (1 + n + npk + E) * B, &rc);
+    if (!d_o) return rc;
+    double *d_c = d_o, *d_g = d_o + B, *d_h = d_g + n * B, *d_p = cost_per_train ? d_h + npk * B : nullptr;
+    if ((rc = launch(d_c, d_g, d_h, d_p)) != CFX_OK) return rc;
+    IDM_HIP(hipMemcpyAsync(cost, d_c, B * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipMemcpyAsync(grad, d_g, n * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipMemcpyAsync(gn, d_h, npk * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (d_p) IDM_HIP(hipMemcpyAsync(cost_per_train, d_p, E * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    IDM_HIP(hipStreamSynchronize(st));
     return CFX_OK;
 }
 
@@ -2873,21 +2892,13 @@ extern "C" int cfx_idm_forces(cfx_idm* s, const cfx_idm_trains* tr, int32_t n_id
     IdmParams ip;
     const double* TH = nullptr;
     hipStream_t st = nullptr;
-    int rc = idm_begin(s, "cfx_idm_forces", tr, false, n_id, param_ids, theta, flags, hip_stream, ip, &TH, &st);
+    const int rc = idm_begin(s, s->ip, idm_check, "cfx_idm_forces", tr, false, n_id, param_ids, theta, flags,
+                             hip_stream, ip, &TH, &st);
     if (rc != CFX_OK) return rc;
-    const size_t nf = (size_t)s->E * ((size_t)s->Nmax + 1) * (size_t)s->B, ns = nf * (size_t)n_id;
-    if (flags & CFX_DEVICE) {
-        IDM_HIP(launch_idm_sens(s->model, s->scheme, idm_dirs(ip), ip, TH, force, sens, st));
+    return idm_forces_staged(s, n_id, force, sens, flags, st, [&](double* F, double* S) -> int {
+        IDM_HIP(launch_idm_sens(s->model, s->scheme, idm_dirs(ip), ip, TH, F, S, st));
         return CFX_OK;
-    }
-    double* d_f = idm_buf(s, 6, nf, &rc);
-    double* d_s = sens ? idm_buf(s, 7, ns, &rc) : nullptr;
-    if (!d_f || (sens && !d_s)) return rc;
-    IDM_HIP(launch_idm_sens(s->model, s->scheme, idm_dirs(ip), ip, TH, d_f, d_s, st));
-    IDM_HIP(hipMemcpyAsync(force, d_f, nf * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (d_s) IDM_HIP(hipMemcpyAsync(sens, d_s, ns * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipStreamSynchronize(st));
-    return CFX_OK;
+    });
 }
 
 extern "C" int cfx_idm_normal(cfx_idm* s, const cfx_idm_trains* tr, int32_t n_id, const int32_t* param_ids,
@@ -2898,24 +2909,15 @@ extern "C" int cfx_idm_normal(cfx_idm* s, const cfx_idm_trains* tr, int32_t n_id
     IdmParams ip;
     const double* TH = nullptr;
     hipStream_t st = nullptr;
-    int rc = idm_begin(s, "cfx_idm_normal", tr, true, n_id, param_ids, theta, flags, hip_stream, ip, &TH, &st);
+    const int rc = idm_begin(s, s->ip, idm_check, "cfx_idm_normal", tr, true, n_id, param_ids, theta, flags,
+                             hip_stream, ip, &TH, &st);
     if (rc != CFX_OK) return rc;
     const int d = idm_dirs(ip);
-    if (flags & CFX_DEVICE) {
-        IDM_HIP(launch_idm_normal(s->model, s->scheme, d, ip, TH, s->d_ws, cost, grad, gn, cost_per_train, st));
-        return CFX_OK;
-    }
-    const size_t B = (size_t)s->B, n = (size_t)n_id, npk = n * (n + 1) / 2, E = (size_t)s->E;
-    double* d_o = idm_buf(s, 8, (1 + n + npk + E) * B, &rc);
-    if (!d_o) return rc;
-    double *d_c = d_o, *d_g = d_o + B, *d_h = d_g + n * B, *d_p = cost_per_train ? d_h + npk * B : nullptr;
-    IDM_HIP(launch_idm_normal(s->model, s->scheme, d, ip, TH, s->d_ws, d_c, d_g, d_h, d_p, st));
-    IDM_HIP(hipMemcpyAsync(cost, d_c, B * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipMemcpyAsync(grad, d_g, n * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipMemcpyAsync(gn, d_h, npk * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (d_p) IDM_HIP(hipMemcpyAsync(cost_per_train, d_p, E * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipStreamSynchronize(st));
-    return CFX_OK;
+    return idm_normal_staged(s, n_id, cost, grad, gn, cost_per_train, flags, st,
+                             [&](double* C, double* G, double* H, double* CPT) -> int {
+                                 IDM_HIP(launch_idm_normal(s->model, s->scheme, d, ip, TH, s->d_ws, C, G, H, CPT, st));
+                                 return CFX_OK;
+                             });
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -3030,40 +3032,6 @@ extern "C" int cfx_idfm_create(int32_t model, const cfx_constants* c, int32_t sc
     return CFX_OK;
 }
 
-// idm_begin for the fatigue kernels: the argument checks, the upload of a host call, fp filled for the launch.
-static int idfm_begin(cfx_idfm* h, const char* fn, const cfx_idm_trains* tr, bool normal, int32_t n_id,
-                      const int32_t* ids, const double* theta, uint32_t flags, void* hip_stream, IdfmParams& fp,
-                      const double** TH, hipStream_t* st) {
-    cfx_idm* s = h->core;
-    const std::string f = std::string(fn) + ": ";
-    if (!tr || !theta) return idm_fail(s, CFX_EINVAL, f + "trains or theta is NULL");
-    if (!tr->times || !tr->act_node || !tr->n_pulses || !tr->truncation || !tr->n_shooting || !tr->final_time ||
-        (s->needs_value && !tr->value))
-        return idm_fail(s, CFX_EINVAL, f + "a train array is NULL");
-    if (normal && (!tr->target || !tr->weight)) return idm_fail(s, CFX_EINVAL, f + "target or weight is NULL");
-    const bool dev = (flags & CFX_DEVICE) != 0;
-    int32_t col[IDF_SLOTS];
-    // with device arrays only the creation arguments and the parameter list can be checked here
-    int rc = idfm_check(fn, s->model, s->scheme, s->m, s->B, s->E, s->P, s->Nmax, true, n_id, ids, col,
-                        dev ? nullptr : tr, s->err);
-    if (rc != CFX_OK) return rc;
-    fp = h->fp;
-    fp.n_id = n_id;
-    for (int k = 0; k < IDF_SLOTS; ++k) fp.col[k] = col[k];
-    IdmTrainPtrs tp;
-    if ((rc = idm_stage(s, fn, tr, normal, n_id, theta, flags, hip_stream, tp, TH, st)) != CFX_OK) return rc;
-    fp.times = tp.times;
-    fp.act = tp.act;
-    fp.value = tp.value;
-    fp.n_pulses = tp.n_pulses;
-    fp.truncation = tp.truncation;
-    fp.n_shooting = tp.n_shooting;
-    fp.final_time = tp.final_time;
-    fp.target = tp.target;
-    fp.weight = tp.weight;
-    return CFX_OK;
-}
-
 extern "C" int cfx_idfm_forces(cfx_idfm* h, const cfx_idm_trains* tr, int32_t n_id, const int32_t* param_ids,
                                const double* theta, double* force, double* sens, uint32_t flags, void* hip_stream) {
     if (!h) return g_create_error = "cfx_idfm_forces: NULL handle", CFX_EINVAL;
@@ -3072,21 +3040,13 @@ extern "C" int cfx_idfm_forces(cfx_idfm* h, const cfx_idm_trains* tr, int32_t n_
     IdfmParams fp;
     const double* TH = nullptr;
     hipStream_t st = nullptr;
-    int rc = idfm_begin(h, "cfx_idfm_forces", tr, false, n_id, param_ids, theta, flags, hip_stream, fp, &TH, &st);
+    const int rc = idm_begin(s, h->fp, idfm_check, "cfx_idfm_forces", tr, false, n_id, param_ids, theta, flags,
+                             hip_stream, fp, &TH, &st);
     if (rc != CFX_OK) return rc;
-    const size_t nf = (size_t)s->E * ((size_t)s->Nmax + 1) * (size_t)s->B, ns = nf * (size_t)n_id;
-    if (flags & CFX_DEVICE) {
-        IDM_HIP(launch_idfm_sens(s->model, s->scheme, fp, TH, force, sens, st));
+    return idm_forces_staged(s, n_id, force, sens, flags, st, [&](double* F, double* S) -> int {
+        IDM_HIP(launch_idfm_sens(s->model, s->scheme, fp, TH, F, S, st));
         return CFX_OK;
-    }
-    double* d_f = idm_buf(s, 6, nf, &rc);
-    double* d_s = sens ? idm_buf(s, 7, ns, &rc) : nullptr;
-    if (!d_f || (sens && !d_s)) return rc;
-    IDM_HIP(launch_idfm_sens(s->model, s->scheme, fp, TH, d_f, d_s, st));
-    IDM_HIP(hipMemcpyAsync(force, d_f, nf * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (d_s) IDM_HIP(hipMemcpyAsync(sens, d_s, ns * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipStreamSynchronize(st));
-    return CFX_OK;
+    });
 }
 
 extern "C" int cfx_idfm_normal(cfx_idfm* h, const cfx_idm_trains* tr, int32_t n_id, const int32_t* param_ids,
@@ -3098,22 +3058,13 @@ extern "C" int cfx_idfm_normal(cfx_idfm* h, const cfx_idm_trains* tr, int32_t n_
     IdfmParams fp;
     const double* TH = nullptr;
     hipStream_t st = nullptr;
-    int rc = idfm_begin(h, "cfx_idfm_normal", tr, true, n_id, param_ids, theta, flags, hip_stream, fp, &TH, &st);
+    const int rc = idm_begin(s, h->fp, idfm_check, "cfx_idfm_normal", tr, true, n_id, param_ids, theta, flags,
+                             hip_stream, fp, &TH, &st);
     if (rc != CFX_OK) return rc;
-    if (flags & CFX_DEVICE) {
-        IDM_HIP(launch_idfm_normal(s->model, s->scheme, fp, TH, s->d_ws, cost, grad, gn, cost_per_train, st));
-        return CFX_OK;
-    }
-    const size_t B = (size_t)s->B, n = (size_t)n_id, npk = n * (n + 1) / 2, E = (size_t)s->E;
-    double* d_o = idm_buf(s, 8, (1 + n + npk + E) * B, &rc);
-    if (!d_o) return rc;
-    double *d_c = d_o, *d_g = d_o + B, *d_h = d_g + n * B, *d_p = cost_per_train ? d_h + npk * B : nullptr;
-    IDM_HIP(launch_idfm_normal(s->model, s->scheme, fp, TH, s->d_ws, d_c, d_g, d_h, d_p, st));
-    IDM_HIP(hipMemcpyAsync(cost, d_c, B * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipMemcpyAsync(grad, d_g, n * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipMemcpyAsync(gn, d_h, npk * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (d_p) IDM_HIP(hipMemcpyAsync(cost_per_train, d_p, E * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipStreamSynchronize(st));
-    return CFX_OK;
+    return idm_normal_staged(s, n_id, cost, grad, gn, cost_per_train, flags, st,
+                             [&](double* C, double* G, double* H, double* CPT) -> int {
+                                 IDM_HIP(launch_idfm_normal(s->model, s->scheme, fp, TH, s->d_ws, C, G, H, CPT, st));
+                                 return CFX_OK;
+                             });
 }
 #undef IDM_HIP

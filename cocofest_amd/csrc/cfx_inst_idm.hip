@@ -2,6 +2,7 @@
 // Hmed2018 without fatigue, RK1 / RK2 / RK4, D = 4 (any subset of the four common parameters) or D = 8 direction
 // slots, and the sum over the trains.
 #include "cfx_idm.h"
+#include "cfx_id_launch.h"
 
 namespace cfx {
 
@@ -32,59 +33,24 @@ __global__ void __launch_bounds__(256) k_idm_reduce(int64_t B, int E, int R, int
         GN[(int64_t)(r - 1 - n) * B + b] = acc;
 }
 
-struct SensArgs {
-    const double* theta;
-    double *force, *sens;
-};
-struct NormalArgs {
-    const double* theta;
-    double* ws;
-};
-
-dim3 grid_of(const IdmParams& P) { return dim3((unsigned)((P.B + kIdmBlock - 1) / kIdmBlock), (unsigned)P.E); }
-
-template <int MODEL, int SCHEME, int D>
-hipError_t run(const IdmParams& P, const SensArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((k_idm_sens<MODEL, SCHEME, D>), grid_of(P), dim3(kIdmBlock), 0, s, P, a.theta, a.force, a.sens);
-    return hipGetLastError();
-}
-template <int MODEL, int SCHEME, int D>
-hipError_t run(const IdmParams& P, const NormalArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((k_idm_normal<MODEL, SCHEME, D>), grid_of(P), dim3(kIdmBlock), 0, s, P, a.theta, a.ws);
-    return hipGetLastError();
-}
-
-template <int MODEL, int D, class Args>
-hipError_t by_scheme(int scheme, const IdmParams& P, const Args& a, hipStream_t s) {
-    switch (scheme) {
-        case 1: return run<MODEL, 1, D>(P, a, s);
-        case 2: return run<MODEL, 2, D>(P, a, s);
-        case 4: return run<MODEL, 4, D>(P, a, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-template <class Args>
-hipError_t dispatch(int model, int scheme, int d, const IdmParams& P, const Args& a, hipStream_t s) {
-    if (d != 4 && d != 8) return hipErrorInvalidValue;
-    switch (model) {
-        case M_D03: return d == 4 ? by_scheme<M_D03, 4>(scheme, P, a, s) : hipErrorInvalidValue;
-        case M_D07: return d == 4 ? by_scheme<M_D07, 4>(scheme, P, a, s) : by_scheme<M_D07, 8>(scheme, P, a, s);
-        case M_H18: return d == 4 ? by_scheme<M_H18, 4>(scheme, P, a, s) : by_scheme<M_H18, 8>(scheme, P, a, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_idm_sens(int model, int scheme, int d, const IdmParams& P, const double* theta, double* force,
                            double* sens, hipStream_t s) {
-    return dispatch(model, scheme, d, P, SensArgs{theta, force, sens}, s);
+    const dim3 grid = id_train_grid(P.B, P.E, kIdmBlock);
+    return id_dispatch(model, scheme, d, [&](auto M, auto S, auto D) {
+        hipLaunchKernelGGL((k_idm_sens<M(), S(), D()>), grid, dim3(kIdmBlock), 0, s, P, theta, force, sens);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_idm_normal(int model, int scheme, int d, const IdmParams& P, const double* theta, double* ws,
                              double* cost, double* grad, double* gn, double* cost_per_train, hipStream_t s) {
-    const hipError_t e = dispatch(model, scheme, d, P, NormalArgs{theta, ws}, s);
+    const dim3 grid = id_train_grid(P.B, P.E, kIdmBlock);
+    const hipError_t e = id_dispatch(model, scheme, d, [&](auto M, auto S, auto D) {
+        hipLaunchKernelGGL((k_idm_normal<M(), S(), D()>), grid, dim3(kIdmBlock), 0, s, P, theta, ws);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return e;
     return launch_idm_reduce(P.B, P.E, P.n_id, ws, cost, grad, gn, cost_per_train, s);
 }
