@@ -28,6 +28,7 @@ from .nmpc import FesNmpc, NmpcFesMsk, NmpcResult
 from .ocp import Axis, Constraint, ConstraintFcn, ConstraintList, FesOcp, Node, Objective, ObjectiveFcn, ObjectiveList, OcpFes
 from .ode_solver import ControlType, OdeSolver
 from .solver import BatchedIpm, IpmOptions, IpmResult, Solver
+from .train_search import TrainSearch, TrainSearchResult
 
 __all__ = [
     "CfxError", "Handle", "load_library", "DingModelFrequency", "DingModelFrequencyWithFatigue",
@@ -35,4 +36,5 @@ __all__ = [
     "DingModelPulseWidthFrequency", "DingModelPulseWidthFrequencyWithFatigue", "FesModel", "ModelMaker",
     "FourierSeries", "FesIdentification", "FesFatigueIdentification", "FesMultiTrainIdentification", "FesMultiTrainFatigueIdentification", "force_at_node", "IvpFes", "IvpSweep", "FesOcp", "Axis", "Constraint", "ConstraintFcn", "ConstraintList", "Node", "Objective", "ObjectiveFcn", "ObjectiveList", "OcpFes",
     "ControlType", "OdeSolver", "FesMskModel", "FesMskOcp", "OcpFesMsk", "FesNmpc", "NmpcFesMsk", "NmpcResult", "BatchedIpm", "IpmOptions", "IpmResult", "Solver",
+    "TrainSearch", "TrainSearchResult",
 ]

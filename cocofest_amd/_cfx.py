@@ -179,6 +179,14 @@ class SweepTrains(C.Structure):
                 ("truncation", C.c_void_p), ("n_shooting", C.c_void_p), ("final_time", C.c_void_p)]
 
 
+class SweepTarget(C.Structure):
+    _fields_ = [("y", C.c_void_p), ("n_samples", C.c_int32), ("sample_dt", C.c_double)]
+
+
+# rows of cfx_sweep_score's metrics [CFX_SWEEP_N_METRICS][B]
+SWEEP_METRICS = ("track", "impulse", "peak", "peak_node", "end_error", "mean_force")
+
+
 class IdmTrains(C.Structure):
     _fields_ = SweepTrains._fields_ + [("target", C.c_void_p), ("weight", C.c_void_p)]
 
@@ -241,6 +249,8 @@ SIGNATURES = {
     "cfx_sweep_check": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                   C.POINTER(SweepTrains)]),
     "cfx_sweep_integrate": (C.c_int, [_P, C.POINTER(SweepTrains), _P, _P, _P, C.c_uint32, _P]),
+    "cfx_sweep_score": (C.c_int, [_P, C.POINTER(SweepTrains), C.POINTER(SweepTarget), _P, _P, _P, C.c_uint32, _P]),
+    "cfx_sweep_target_check": (C.c_int, [C.POINTER(SweepTarget)]),
     "cfx_sweep_last_error": (C.c_char_p, [_P]),
     "cfx_sweep_destroy": (None, [_P]),
     "cfx_idm_create": (C.c_int, [C.c_int32, C.POINTER(Constants), C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
@@ -984,6 +994,17 @@ def sweep_check(model_id, scheme, n_steps, batch, max_pulses, max_shooting, trai
         raise CfxError(rc, lib.cfx_last_error(None).decode())
 
 
+def sweep_target_check(target, sample_dt):
+    """cfx_sweep_target_check: the checks of a host target force ((n_samples,) samples, ``sample_dt``), without a
+    device.  Raises ``CfxError`` with the library's message."""
+    lib = load_library()
+    y = np.ascontiguousarray(target, dtype=np.float64)
+    tg = SweepTarget(_ptr(y) if y.size else None, int(y.size), float(sample_dt))
+    rc = lib.cfx_sweep_target_check(C.byref(tg))
+    if rc != OK:
+        raise CfxError(rc, lib.cfx_last_error(None).decode())
+
+
 class Sweep:
     """One cfx_sweep: single shooting of B instances of one model, every instance with its own stimulation train
     (``trains``: the arrays of ``cfx_sweep_trains``, SoA).  Host numpy arrays are checked, copied and the call
@@ -1033,6 +1054,44 @@ class Sweep:
         if rc != OK:
             raise CfxError(rc, self.lib.cfx_sweep_last_error(self.h).decode())
         return final, out
+
+    def score(self, trains: dict, target, sample_dt, x0=None):
+        """cfx_sweep_score: final states (nx, B) and the metrics (len(SWEEP_METRICS), B) of every instance's node
+        forces against the target force ``target`` ((n_samples,) values at t = j ``sample_dt``; piecewise linear,
+        the last sample held).  numpy arrays, or CUDA tensors throughout (``target`` too).  Returns (final, metrics)."""
+        B, nx, nm = self.batch, self.nx, len(SWEEP_METRICS)
+        on_device = _is_tensor(trains.get("times"))
+        st, keep = _sweep_trains(trains, B, self.max_pulses, self.needs_value, self.device if on_device else None)
+        if on_device:
+            import torch
+
+            dev = f"cuda:{self.device}"
+            if x0 is not None and not (_is_tensor(x0) and x0.is_cuda and x0.dtype == torch.float64
+                                       and x0.is_contiguous() and tuple(x0.shape) == (nx, B)):
+                raise CfxError(EINVAL, f"sweep: x0 must be a contiguous float64 ({nx}, {B}) tensor on {dev}")
+            if not (_is_tensor(target) and target.is_cuda and target.device.index == self.device
+                    and target.dtype == torch.float64 and target.is_contiguous() and target.dim() == 1):
+                raise CfxError(EINVAL, f"sweep: target must be a contiguous 1-D float64 tensor on {dev}")
+            final = torch.empty((nx, B), dtype=torch.float64, device=dev)
+            metrics = torch.empty((nm, B), dtype=torch.float64, device=dev)
+            stream, fl = torch.cuda.current_stream().cuda_stream, DEVICE
+        else:
+            if x0 is not None:
+                x0 = np.ascontiguousarray(x0, dtype=np.float64)
+                if x0.shape != (nx, B):
+                    raise CfxError(EINVAL, f"sweep: x0 must have shape ({nx}, {B}), not {x0.shape}")
+            target = np.ascontiguousarray(target, dtype=np.float64)
+            if target.ndim != 1:
+                raise CfxError(EINVAL, "sweep: target must be 1-D")
+            final = np.empty((nx, B))
+            metrics = np.empty((nm, B))
+            stream, fl = None, 0
+        tg = SweepTarget(_ptr(target), int(target.shape[0]), float(sample_dt))
+        rc = self.lib.cfx_sweep_score(self.h, C.byref(st), C.byref(tg), _ptr(x0), _ptr(final), _ptr(metrics), fl,
+                                      stream)
+        if rc != OK:
+            raise CfxError(rc, self.lib.cfx_sweep_last_error(self.h).decode())
+        return final, metrics
 
     def close(self):
         if getattr(self, "h", None):

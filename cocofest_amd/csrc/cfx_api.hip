@@ -2319,8 +2319,9 @@ struct cfx_sweep {
     bool needs_value = false;
     SweepParams sp{};
     hipStream_t stream = nullptr;
-    // staging of host calls: times, value, final_time, x0, xf, nodes (doubles); act + the three counts (int32)
-    DevBuf dbuf[6];
+    // staging of host calls: times, value, final_time, x0, xf, nodes, target, metrics (doubles); act + the three
+    // counts (int32)
+    DevBuf dbuf[8];
     int32_t* d_int = nullptr;
     std::string err;
 };
@@ -2461,16 +2462,45 @@ static double* sweep_buf(cfx_sweep* s, int slot, size_t n, int* rc) {
     return b.p;
 }
 
-extern "C" int cfx_sweep_integrate(cfx_sweep* s, const cfx_sweep_trains* tr, const double* x0, double* final_state,
-                                   double* nodes, uint32_t flags, void* hip_stream) {
-    if (!s) return g_create_error = "cfx_sweep_integrate: NULL handle", CFX_EINVAL;
-    if (!tr || !final_state) return sweep_fail(s, CFX_EINVAL, "cfx_sweep_integrate: trains or final_state is NULL");
+static_assert(kSweepMetrics == CFX_SWEEP_N_METRICS, "metric rows of k_sweep and of cfx.h differ");
+
+// The checks of a target force; host: the samples too (a device caller is responsible for them).
+static int sweep_target_check(const char* fn, const cfx_sweep_target* tg, bool host, std::string& msg) {
+    const std::string f = std::string(fn) + ": ";
+    if (!tg) return msg = f + "target is NULL", CFX_EINVAL;
+    if (tg->n_samples < 1) return msg = f + "target: n_samples must be >= 1", CFX_EINVAL;
+    if (tg->n_samples > 1 && !(tg->sample_dt > 0.0)) return msg = f + "target: sample_dt must be positive", CFX_EINVAL;
+    if (!tg->y) return msg = f + "target: y is NULL", CFX_EINVAL;
+    if (host)
+        for (int32_t j = 0; j < tg->n_samples; ++j)
+            if (!std::isfinite(tg->y[j]))
+                return msg = f + "target: y[" + std::to_string(j) + "] is not finite", CFX_EINVAL;
+    return CFX_OK;
+}
+
+extern "C" int cfx_sweep_target_check(const cfx_sweep_target* target) {
+    return sweep_target_check("cfx_sweep_target_check", target, true, g_create_error);
+}
+
+// cfx_sweep_integrate (tg == nullptr) and cfx_sweep_score (tg, metrics; no nodes): one staging path, one launch.
+static int sweep_run(const char* fn, cfx_sweep* s, const cfx_sweep_trains* tr, const cfx_sweep_target* tg,
+                     const double* x0, double* final_state, double* nodes, double* metrics, uint32_t flags,
+                     void* hip_stream) {
+    const std::string f = std::string(fn) + ": ";
     if (!tr->times || !tr->act_node || !tr->n_pulses || !tr->truncation || !tr->n_shooting || !tr->final_time ||
         (s->needs_value && !tr->value))
-        return sweep_fail(s, CFX_EINVAL, "cfx_sweep_integrate: a train array is NULL");
+        return sweep_fail(s, CFX_EINVAL, f + "a train array is NULL");
     const size_t B = (size_t)s->B, P = (size_t)s->P, nx = (size_t)s->nx, nn = (size_t)s->Nmax + 1;
+    const size_t nt = tg ? (size_t)tg->n_samples : 0;
     SweepParams sp = s->sp;
-    if (hipSetDevice(s->device) != hipSuccess) return sweep_fail(s, CFX_EHIP, "cfx_sweep_integrate: hipSetDevice failed");
+    if (tg) {
+        sp.tn = tg->n_samples;
+        sp.inv_sdt = tg->n_samples > 1 ? 1.0 / tg->sample_dt : 1.0;
+    }
+    const auto launch = [&](hipStream_t st) {
+        return tg ? launch_sweep_score(s->model, s->scheme, sp, st) : launch_sweep(s->model, s->scheme, sp, st);
+    };
+    if (hipSetDevice(s->device) != hipSuccess) return sweep_fail(s, CFX_EHIP, f + "hipSetDevice failed");
     if (flags & CFX_DEVICE) {
         sp.times = tr->times;
         sp.act = tr->act_node;
@@ -2482,25 +2512,32 @@ extern "C" int cfx_sweep_integrate(cfx_sweep* s, const cfx_sweep_trains* tr, con
         sp.x0 = x0;
         sp.xf = final_state;
         sp.nodes = nodes;
-        const hipError_t e = launch_sweep(s->model, s->scheme, sp, (hipStream_t)hip_stream);
-        if (e != hipSuccess) return sweep_fail(s, CFX_EHIP, std::string("cfx_sweep_integrate: ") + hipGetErrorString(e));
+        if (tg) sp.ty = tg->y;
+        sp.metrics = metrics;
+        const hipError_t e = launch((hipStream_t)hip_stream);
+        if (e != hipSuccess) return sweep_fail(s, CFX_EHIP, f + hipGetErrorString(e));
         return CFX_OK;
     }
-    int rc = sweep_check("cfx_sweep_integrate", s->model, s->scheme, s->m, s->B, s->P, s->Nmax, tr, s->err);
+    int rc = sweep_check(fn, s->model, s->scheme, s->m, s->B, s->P, s->Nmax, tr, s->err);
     if (rc != CFX_OK) return rc;
+    if (tg && (rc = sweep_target_check(fn, tg, true, s->err)) != CFX_OK) return rc;
     if (x0)
         for (size_t i = 0; i < nx * B; ++i)
-            if (!std::isfinite(x0[i])) return sweep_fail(s, CFX_EINVAL, "cfx_sweep_integrate: x0 is not finite");
+            if (!std::isfinite(x0[i])) return sweep_fail(s, CFX_EINVAL, f + "x0 is not finite");
     double* d_t = sweep_buf(s, 0, P * B, &rc);
     double* d_v = s->needs_value ? sweep_buf(s, 1, P * B, &rc) : nullptr;
     double* d_tf = sweep_buf(s, 2, B, &rc);
     double* d_x0 = x0 ? sweep_buf(s, 3, nx * B, &rc) : nullptr;
     double* d_xf = sweep_buf(s, 4, nx * B, &rc);
     double* d_nd = nodes ? sweep_buf(s, 5, nn * nx * B, &rc) : nullptr;
-    if (!d_t || (s->needs_value && !d_v) || !d_tf || (x0 && !d_x0) || !d_xf || (nodes && !d_nd)) return rc;
+    double* d_ty = tg ? sweep_buf(s, 6, nt, &rc) : nullptr;
+    double* d_mt = tg ? sweep_buf(s, 7, (size_t)kSweepMetrics * B, &rc) : nullptr;
+    if (!d_t || (s->needs_value && !d_v) || !d_tf || (x0 && !d_x0) || !d_xf || (nodes && !d_nd) ||
+        (tg && (!d_ty || !d_mt)))
+        return rc;
     if (!s->d_int && hipMalloc(&s->d_int, (P + 3) * B * sizeof(int32_t)) != hipSuccess) {
         s->d_int = nullptr;
-        return sweep_fail(s, CFX_ENOMEM, "cfx_sweep_integrate: hipMalloc failed");
+        return sweep_fail(s, CFX_ENOMEM, f + "hipMalloc failed");
     }
     int32_t* d_act = s->d_int;
     int32_t* d_cnt = s->d_int + P * B;
@@ -2514,6 +2551,7 @@ extern "C" int cfx_sweep_integrate(cfx_sweep* s, const cfx_sweep_trains* tr, con
     if (d_v) SWEEP_HIP(hipMemcpyAsync(d_v, tr->value, P * B * sizeof(double), hipMemcpyHostToDevice, st));
     SWEEP_HIP(hipMemcpyAsync(d_tf, tr->final_time, B * sizeof(double), hipMemcpyHostToDevice, st));
     if (d_x0) SWEEP_HIP(hipMemcpyAsync(d_x0, x0, nx * B * sizeof(double), hipMemcpyHostToDevice, st));
+    if (d_ty) SWEEP_HIP(hipMemcpyAsync(d_ty, tg->y, nt * sizeof(double), hipMemcpyHostToDevice, st));
     SWEEP_HIP(hipMemcpyAsync(d_act, tr->act_node, P * B * sizeof(int32_t), hipMemcpyHostToDevice, st));
     SWEEP_HIP(hipMemcpyAsync(d_cnt, tr->n_pulses, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
     SWEEP_HIP(hipMemcpyAsync(d_cnt + B, tr->truncation, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -2528,12 +2566,34 @@ extern "C" int cfx_sweep_integrate(cfx_sweep* s, const cfx_sweep_trains* tr, con
     sp.x0 = d_x0;
     sp.xf = d_xf;
     sp.nodes = d_nd;
-    SWEEP_HIP(launch_sweep(s->model, s->scheme, sp, st));
+    sp.ty = d_ty;
+    sp.metrics = d_mt;
+    SWEEP_HIP(launch(st));
     SWEEP_HIP(hipMemcpyAsync(final_state, d_xf, nx * B * sizeof(double), hipMemcpyDeviceToHost, st));
     if (d_nd) SWEEP_HIP(hipMemcpyAsync(nodes, d_nd, nn * nx * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (d_mt)
+        SWEEP_HIP(hipMemcpyAsync(metrics, d_mt, (size_t)kSweepMetrics * B * sizeof(double), hipMemcpyDeviceToHost, st));
     SWEEP_HIP(hipStreamSynchronize(st));
 #undef SWEEP_HIP
     return CFX_OK;
+}
+
+extern "C" int cfx_sweep_integrate(cfx_sweep* s, const cfx_sweep_trains* tr, const double* x0, double* final_state,
+                                   double* nodes, uint32_t flags, void* hip_stream) {
+    if (!s) return g_create_error = "cfx_sweep_integrate: NULL handle", CFX_EINVAL;
+    if (!tr || !final_state) return sweep_fail(s, CFX_EINVAL, "cfx_sweep_integrate: trains or final_state is NULL");
+    return sweep_run("cfx_sweep_integrate", s, tr, nullptr, x0, final_state, nodes, nullptr, flags, hip_stream);
+}
+
+extern "C" int cfx_sweep_score(cfx_sweep* s, const cfx_sweep_trains* tr, const cfx_sweep_target* tg, const double* x0,
+                               double* final_state, double* metrics, uint32_t flags, void* hip_stream) {
+    if (!s) return g_create_error = "cfx_sweep_score: NULL handle", CFX_EINVAL;
+    if (!tr || !tg || !final_state || !metrics)
+        return sweep_fail(s, CFX_EINVAL, "cfx_sweep_score: trains, target, final_state or metrics is NULL");
+    // n_samples and sample_dt are host values with CFX_DEVICE too
+    const int rc = sweep_target_check("cfx_sweep_score", tg, false, s->err);
+    if (rc != CFX_OK) return rc;
+    return sweep_run("cfx_sweep_score", s, tr, tg, x0, final_state, nullptr, metrics, flags, hip_stream);
 }
 
 extern "C" int cfx_gather_sum(int64_t batch, int64_t n_dst, const int32_t* ptr, const int32_t* idx, const double* src,

@@ -1,4 +1,4 @@
-// cfx_sweep.h — gfx950 kernel of the stimulation-train sweep (cfx_sweep_integrate).
+// cfx_sweep.h — gfx950 kernel of the stimulation-train sweep (cfx_sweep_integrate, cfx_sweep_score).
 //
 // One thread per instance, and every instance carries its OWN train: pulse times, pulse count, truncation,
 // n_shooting, final_time and per-pulse widths / intensities.  Single shooting from the rest state (or a given x0)
@@ -52,7 +52,24 @@ struct SweepParams {
     const double* x0;   // [nx][B] or nullptr: the rest state
     double* xf;         // [nx][B]
     double* nodes;      // [(Nmax + 1)][nx][B] or nullptr
+    // k_sweep<.., SCORE = true> only (cfx_sweep_score): the target force and the metrics
+    const double* ty;   // [tn] samples of the target at t = j * sample_dt
+    int32_t tn;         // >= 1
+    double inv_sdt;     // 1.0 / sample_dt
+    double* metrics;    // [kSweepMetrics][B]
 };
+
+constexpr int kSweepMetrics = 6;  // CFX_SWEEP_N_METRICS: track, impulse, peak, peak_node, end_error, mean_force
+
+// The target force at time t >= 0: piecewise linear through the samples, the last one held beyond the table.
+__device__ __forceinline__ double sweep_target(const SweepParams& P, double t) {
+    const int last = P.tn - 1;
+    const double u = t * P.inv_sdt;
+    if (last == 0 || !(u < (double)last)) return P.ty[last];  // floor(u) >= tn - 1
+    const int j = (int)floor(u);
+    const double y0 = P.ty[j];
+    return fma(u - (double)j, P.ty[j + 1] - y0, y0);
+}
 
 // One right-hand side.  x = (cn, F[, A, Tau1, Km]); cs: the calcium forcing at the stage time; amp: Ding2007 E(pw).
 template <int MODEL>
@@ -86,7 +103,11 @@ __device__ __forceinline__ void sweep_rhs(const SweepParams& P, double cs, doubl
 // a sorted batch over more compute units and a block's registers are freed as soon as its own wave is done.
 constexpr int kSweepBlock = 64;
 
-template <int MODEL, int SCHEME>
+// SCORE (cfx_sweep_score): the same rollout, with the functionals of the node forces F_0..F_N against the target
+// carried in registers: sum_k (F_k - y(t_k))^2, the trapezoid sum, the peak and its first node.  The target is read
+// at the node times only (N + 1 lookups), the sums run sequentially in k, and the six metrics are written once at
+// the end; no node is written.  SCORE = false compiles to the code it was before the parameter existed.
+template <int MODEL, int SCHEME, bool SCORE = false>
 __global__ void __launch_bounds__(kSweepBlock) k_sweep(const SweepParams P) {
     constexpr int NX = nx_of(MODEL);
     const int64_t B = P.B;
@@ -111,6 +132,15 @@ __global__ void __launch_bounds__(kSweepBlock) k_sweep(const SweepParams P) {
     if (P.nodes != nullptr) {
 #pragma unroll
         for (int r = 0; r < NX; ++r) P.nodes[(int64_t)r * B + b] = x[r];
+    }
+    // SCORE: node 0 counts, with F_0 from x0
+    double trk = 0.0, trap = 0.0, peak = 0.0, err = 0.0;
+    int peak_node = 0;
+    if constexpr (SCORE) {
+        err = x[1] - sweep_target(P, 0.0);
+        trk = err * err;
+        trap = 0.5 * x[1];
+        peak = x[1];
     }
 
     int nv = 0;  // visible pulses
@@ -176,9 +206,28 @@ __global__ void __launch_bounds__(kSweepBlock) k_sweep(const SweepParams P) {
 #pragma unroll
             for (int r = 0; r < NX; ++r) P.nodes[((int64_t)(k + 1) * NX + r) * B + b] = x[r];
         }
+        if constexpr (SCORE) {
+            const double F = x[1];
+            err = F - sweep_target(P, (double)(k + 1) * dt);
+            trk = fma(err, err, trk);
+            trap += k + 1 < N ? F : 0.5 * F;
+            if (F > peak) {
+                peak = F;
+                peak_node = k + 1;
+            }
+        }
     }
 #pragma unroll
     for (int r = 0; r < NX; ++r) P.xf[(int64_t)r * B + b] = x[r];
+    if constexpr (SCORE) {
+        const double impulse = dt * trap;
+        P.metrics[b] = dt * trk;
+        P.metrics[B + b] = impulse;
+        P.metrics[2 * B + b] = peak;
+        P.metrics[3 * B + b] = (double)peak_node;
+        P.metrics[4 * B + b] = err;  // of the last node
+        P.metrics[5 * B + b] = impulse / P.final_time[b];
+    }
     if (P.nodes != nullptr) {
         const double nan = __builtin_nan("");
         for (int k = N + 1; k <= P.Nmax; ++k) {
@@ -189,5 +238,6 @@ __global__ void __launch_bounds__(kSweepBlock) k_sweep(const SweepParams P) {
 }
 
 hipError_t launch_sweep(int model, int scheme, const SweepParams& P, hipStream_t s);
+hipError_t launch_sweep_score(int model, int scheme, const SweepParams& P, hipStream_t s);  // k_sweep<.., true>
 
 }  // namespace cfx

@@ -90,22 +90,7 @@ class IvpFes:
             raise ValueError("ivp_parameters must be a dictionary")
         if not isinstance(fes["model"], FesModel):
             raise TypeError("model must be a FesModel type")
-        model = fes["model"]
-        if isinstance(model, DingModelPulseWidthFrequency | DingModelPulseWidthFrequencyWithFatigue):
-            pw = fes["pulse_width"]
-            if isinstance(pw, bool) or not isinstance(pw, int | float | list):
-                raise TypeError("pulse_width must be int, float or list type")
-            ok = all(p >= model.pd0 for p in pw) if isinstance(pw, list) else pw >= model.pd0
-            if not ok:
-                raise ValueError("pulse width must be greater than minimum pulse width")
-        if isinstance(model, DingModelPulseIntensityFrequency | DingModelPulseIntensityFrequencyWithFatigue):
-            pi = fes["pulse_intensity"]
-            if isinstance(pi, bool) or not isinstance(pi, int | float | list):
-                raise TypeError("pulse_intensity must be int, float or list type")
-            imin = model.min_pulse_intensity()
-            ok = all(p >= imin for p in pi) if isinstance(pi, list) else bool(pi >= imin)
-            if not ok:
-                raise ValueError("Pulse intensity must be greater than minimum pulse intensity")
+        check_pulse_values(fes["model"], fes["pulse_width"], fes["pulse_intensity"])
         if not isinstance(fes["pulse_mode"], str):
             raise ValueError("pulse_mode must be a string type")
         if not isinstance(ivp["final_time"], int | float):
@@ -123,14 +108,7 @@ class IvpFes:
         (ivp_fes.py:232-256; the write-back is the reference's behaviour)."""
         if self.pulse_mode == "single":
             return
-        if self.pulse_mode == "doublet":
-            extra = [[round(t + 0.005, 3) for t in self.stim_time]]
-        elif self.pulse_mode == "triplet":
-            extra = [[round(t + 0.005, 3) for t in self.stim_time], [round(t + 0.01, 3) for t in self.stim_time]]
-        else:
-            raise ValueError("Pulse mode not yet implemented")
-        self.stim_time = self.stim_time + [t for e in extra for t in e]
-        self.stim_time.sort()
+        self.stim_time = expand_pulse_mode(self.stim_time, self.pulse_mode)
         self.model.stim_time = self.stim_time
         self.n_stim = len(self.stim_time)
         if self._n_shooting_given is None:
@@ -252,6 +230,39 @@ class IvpFes:
         return cls(fes_parameters, ivp_parameters)
 
 
+def check_pulse_values(model, pulse_width, pulse_intensity):
+    """The pulse-width (Ding2007) / pulse-intensity (Hmed2018) checks of ``IvpFes.dictionaries_check``."""
+    if isinstance(model, DingModelPulseWidthFrequency | DingModelPulseWidthFrequencyWithFatigue):
+        pw = pulse_width
+        if isinstance(pw, bool) or not isinstance(pw, int | float | list):
+            raise TypeError("pulse_width must be int, float or list type")
+        ok = all(p >= model.pd0 for p in pw) if isinstance(pw, list) else pw >= model.pd0
+        if not ok:
+            raise ValueError("pulse width must be greater than minimum pulse width")
+    if isinstance(model, DingModelPulseIntensityFrequency | DingModelPulseIntensityFrequencyWithFatigue):
+        pi = pulse_intensity
+        if isinstance(pi, bool) or not isinstance(pi, int | float | list):
+            raise TypeError("pulse_intensity must be int, float or list type")
+        imin = model.min_pulse_intensity()
+        ok = all(p >= imin for p in pi) if isinstance(pi, list) else bool(pi >= imin)
+        if not ok:
+            raise ValueError("Pulse intensity must be greater than minimum pulse intensity")
+
+
+def expand_pulse_mode(stim_time: list, pulse_mode: str) -> list:
+    """The train after its pulse mode: doublets / triplets add pulses 5 and 10 ms after each one (ivp_fes.py:232-256);
+    a new sorted list ("single": the list itself)."""
+    if pulse_mode == "single":
+        return stim_time
+    if pulse_mode == "doublet":
+        extra = [[round(t + 0.005, 3) for t in stim_time]]
+    elif pulse_mode == "triplet":
+        extra = [[round(t + 0.005, 3) for t in stim_time], [round(t + 0.01, 3) for t in stim_time]]
+    else:
+        raise ValueError("Pulse mode not yet implemented")
+    return sorted(stim_time + [t for e in extra for t in e])
+
+
 def activation_nodes(stim_time, n_shooting: int, final_time) -> list:
     """Per pulse, the first node k with t_i <= k final_time / n_shooting, in the exact rational arithmetic of
     ``get_numerical_data_time_series`` (a pulse before t = 0 is visible from node 0; a value above ``n_shooting``
@@ -264,34 +275,82 @@ def activation_nodes(stim_time, n_shooting: int, final_time) -> list:
     return out
 
 
-def pack_train(ivp: IvpFes) -> dict:
-    """What the sweep kernel needs of one ``IvpFes``: pulse times, activation nodes, per-pulse widths (Ding2007) or
-    intensities (Hmed2018), truncation, n_shooting, final_time.  Pulses that no node sees are left out.
+def pack_train_fields(model, stim_time, n_shooting, final_time, truncation, pulse_width=None,
+                      pulse_intensity=None) -> dict:
+    """What the sweep kernel needs of one train (``stim_time`` after its pulse mode): pulse times, activation nodes,
+    per-pulse widths (Ding2007) or intensities (Hmed2018), truncation, n_shooting, final_time.  Pulses that no node
+    sees are left out.
 
     Ding2007: ``IvpFes._build_controls`` gives interval k the width ``pulse_width[min(v, N + 1) - 1]`` where v is the
     number of visible pulses (the reference's ``stim_idx_at_node_list`` is cut from a list of N + 1 nodes), so pulse i
     carries ``pulse_width[min(i, N)]``: the interval widths are the ones ``IvpFes.integrate`` uses."""
-    times = [float(t) for t in ivp.stim_time]
+    times = [float(t) for t in stim_time]
     if any(b < a for a, b in zip(times, times[1:])):
         raise ValueError("stim_time must be sorted")
-    N = int(ivp.n_shooting)
-    act = activation_nodes(ivp.stim_time, N, ivp.final_time)
+    N = int(n_shooting)
+    act = activation_nodes(stim_time, N, final_time)
     n = sum(1 for a in act if a <= N)
     value = None
-    if isinstance(ivp.model, DingModelPulseWidthFrequency):
-        pw = ivp.pulse_width
+    if isinstance(model, DingModelPulseWidthFrequency):
+        pw = pulse_width
         if isinstance(pw, list) and len(pw) != 1:
             value = [float(pw[min(i, N, len(pw) - 1)]) for i in range(n)]
         else:
             value = [float(pw[0] if isinstance(pw, list) else pw)] * n
-    elif isinstance(ivp.model, DingModelPulseIntensityFrequency):
-        pi = ivp.pulse_intensity
+    elif isinstance(model, DingModelPulseIntensityFrequency):
+        pi = pulse_intensity
         if isinstance(pi, list) and len(pi) != 1:
             value = [float(pi[i]) for i in range(n)]
         else:
             value = [float(pi[0] if isinstance(pi, list) else pi)] * n
-    return {"times": times[:n], "act_node": act[:n], "value": value, "truncation": int(ivp.model._sum_stim_truncation),
-            "n_shooting": N, "final_time": float(ivp.final_time)}
+    return {"times": times[:n], "act_node": act[:n], "value": value, "truncation": int(truncation),
+            "n_shooting": N, "final_time": float(final_time)}
+
+
+def pack_train(ivp: IvpFes) -> dict:
+    """``pack_train_fields`` of one ``IvpFes``."""
+    return pack_train_fields(ivp.model, ivp.stim_time, ivp.n_shooting, ivp.final_time,
+                             ivp.model._sum_stim_truncation, ivp.pulse_width, ivp.pulse_intensity)
+
+
+_TRAIN_KEYS = {"stim_time", "final_time", "n_shooting", "pulse_mode", "sum_stim_truncation", "pulse_width",
+               "pulse_intensity"}
+
+
+def pack_train_dict(model, train: dict) -> dict:
+    """``pack_train_fields`` of one train dict (keys: ``stim_time``, ``final_time``, and optionally ``n_shooting``
+    (None: the ``OcpFes.prepare_n_shooting`` rule), ``pulse_mode``, ``sum_stim_truncation`` (None: the model's),
+    ``pulse_width`` / ``pulse_intensity``), with ``IvpFes``'s defaults, checks and messages, and no ``IvpFes``."""
+    if not isinstance(train, dict):
+        raise TypeError("a train must be a dictionary")
+    unknown = set(train) - _TRAIN_KEYS
+    if unknown:
+        raise ValueError(f"unknown keys {sorted(unknown)}")
+    stim_time = train.get("stim_time")
+    if not isinstance(stim_time, list):
+        raise TypeError("stim_time must be a list")
+    final_time = train.get("final_time")
+    if isinstance(final_time, bool) or not isinstance(final_time, int | float):
+        raise ValueError("final_time must be an int or float type")
+    if not final_time > 0:
+        raise ValueError("final_time must be positive")
+    ns = train.get("n_shooting")
+    if ns is not None and (isinstance(ns, bool) or not isinstance(ns, int) or ns < 1):
+        raise ValueError("n_shooting must be a positive int (or None for the stimulation-time LCM rule)")
+    pulse_mode = train.get("pulse_mode", "single")
+    if not isinstance(pulse_mode, str):
+        raise ValueError("pulse_mode must be a string type")
+    T = train.get("sum_stim_truncation")
+    T = model._sum_stim_truncation if T is None else T
+    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+        raise ValueError("sum_stim_truncation must be a positive int")
+    pulse_width = train.get("pulse_width", 0.0003)  # IvpFes's defaults
+    pulse_intensity = train.get("pulse_intensity", 50)
+    check_pulse_values(model, pulse_width, pulse_intensity)
+    stim_time = expand_pulse_mode(stim_time, pulse_mode)
+    if ns is None:
+        ns = OcpFes.prepare_n_shooting(stim_time, final_time)
+    return pack_train_fields(model, stim_time, ns, final_time, T, pulse_width, pulse_intensity)
 
 
 def sweep_order(work) -> np.ndarray:
@@ -330,17 +389,53 @@ class IvpSweep:
                 raise ValueError(f"ivps[{i}]: ode_solver differs from ivps[0]'s")
             if any(t != PLACEHOLDER_TIME for t in ivp.model.previous_stim["time"]):
                 raise ValueError(f"ivps[{i}]: previous_stim is not supported by IvpSweep")
-        self.model = first.model
-        self.ode_solver = solver
-        self.batch = len(ivps)
-        self.device = device
         trains = []
         for i, ivp in enumerate(ivps):
             try:
                 trains.append(pack_train(ivp))
             except ValueError as e:
                 raise ValueError(f"ivps[{i}]: {e}") from None
+        self._setup(first.model, solver, trains, device)
+
+    @classmethod
+    def from_trains(cls, model, trains, ode_solver=None, device: int = 0):
+        """The sweep of a list of train dicts on one model, packed directly: no ``IvpFes`` is constructed.
+
+        A train: ``{"stim_time": [...], "final_time": tf}`` and optionally ``"n_shooting"`` (None: the
+        ``OcpFes.prepare_n_shooting`` rule on the train after its pulse mode), ``"pulse_mode"`` ("single"),
+        ``"sum_stim_truncation"`` (None: the model's), ``"pulse_width"`` (Ding2007) / ``"pulse_intensity"`` (Hmed2018):
+        a value or one per pulse.  The packed arrays are those of ``IvpSweep([IvpFes(...), ...])`` for the same
+        trains; ``model.stim_time`` is not used and the model is not modified.  ``ode_solver``: RK1 / RK2 / RK4,
+        default ``OdeSolver.RK4(n_integration_steps=10)``.  Errors name the offending ``trains[i]``."""
+        if not isinstance(model, FesModel):
+            raise TypeError("model must be a FesModel type")
+        solver = OdeSolver.RK4(n_integration_steps=10) if ode_solver is None else ode_solver
+        if not isinstance(solver, (OdeSolver.RK1, OdeSolver.RK2, OdeSolver.RK4)):
+            raise ValueError("ode_solver must be an OdeSolver.RK1, RK2 or RK4 (OdeSolver.COLLOCATION is not supported "
+                             "by IvpSweep)")
+        if any(t != PLACEHOLDER_TIME for t in model.previous_stim["time"]):
+            raise ValueError("previous_stim is not supported by IvpSweep")
+        trains = list(trains)
+        if not trains:
+            raise ValueError("IvpSweep needs at least one train")
+        packed = []
+        for i, train in enumerate(trains):
+            try:
+                packed.append(pack_train_dict(model, train))
+            except (TypeError, ValueError, IndexError) as e:
+                raise type(e)(f"trains[{i}]: {e}") from None
+        self = cls.__new__(cls)
+        self._setup(model, solver, packed, device)
+        return self
+
+    def _setup(self, model, solver, trains, device):
+        """Sort, pack and check the ``pack_train_fields`` dicts of the batch (in the caller's order)."""
+        self.model = model
+        self.ode_solver = solver
+        self.batch = len(trains)
+        self.device = device
         self.n_shooting = np.array([t["n_shooting"] for t in trains], dtype=np.int32)
+        self.final_time = np.array([t["final_time"] for t in trains], dtype=np.float64)
         m = solver.n_integration_steps
         work = [t["n_shooting"] * m * max(1, min(t["truncation"], len(t["times"]))) for t in trains]
         self.order = sweep_order(work)
@@ -383,14 +478,9 @@ class IvpSweep:
 
         Returns {state: (B,)}, the final states, in the order of ``ivps``.  ``nodes=True``: {state: (B, N_max + 1)},
         the node states, NaN past an instance's own ``n_shooting``, plus ``"n_shooting"``: (B,)."""
-        nx, B = self.model.nb_state, self.batch
+        B = self.batch
         if x0 is not None:
-            x0 = np.asarray(x0, dtype=np.float64)
-            if x0.shape == (nx,):
-                x0 = np.broadcast_to(x0, (B, nx))
-            if x0.shape != (B, nx):
-                raise ValueError(f"x0 must have shape ({nx},) or ({B}, {nx})")
-            x0 = np.ascontiguousarray(x0[self.order].T)
+            x0 = self._start_states(x0)
         final, traj = self.sweep().integrate(self.trains, x0=x0, nodes=nodes)
         inverse = np.empty(B, dtype=np.int64)
         inverse[self.order] = np.arange(B)
@@ -399,6 +489,40 @@ class IvpSweep:
             return {name: final[i, inverse].copy() for i, name in enumerate(names)}
         result = {name: traj[:, i, :].T[inverse].copy() for i, name in enumerate(names)}
         result["n_shooting"] = self.n_shooting.copy()
+        return result
+
+    def _start_states(self, x0):
+        """``x0`` ((nx,) for all, or (B, nx), caller's order) as the (nx, B) array of the launch order."""
+        nx, B = self.model.nb_state, self.batch
+        x0 = np.asarray(x0, dtype=np.float64)
+        if x0.shape == (nx,):
+            x0 = np.broadcast_to(x0, (B, nx))
+        if x0.shape != (B, nx):
+            raise ValueError(f"x0 must have shape ({nx},) or ({B}, {nx})")
+        return np.ascontiguousarray(x0[self.order].T)
+
+    def score(self, target, sample_dt=None, x0=None) -> dict:
+        """Integrate every instance as ``integrate`` does and score its node forces F_0..F_N against a target force,
+        on the device (``cfx_sweep_score``): no node trajectory is written.
+
+        ``target``: a scalar (a constant target) or a 1-D array of samples at t = j ``sample_dt``, piecewise linear
+        between them and held at the last one beyond the table.  Returns {state: (B,)}, the final states, plus
+        ``track`` (dt sum_k (F_k - y(t_k))^2), ``impulse`` (the trapezoid of F over the nodes), ``peak`` and
+        ``peak_node`` (int: the first node that attains it), ``end_error`` (F_N - y(final_time)) and ``mean_force``
+        (impulse / final_time): each (B,), in the caller's order."""
+        y = np.atleast_1d(np.asarray(target, dtype=np.float64))
+        if y.ndim != 1 or y.size < 1:
+            raise ValueError("target must be a scalar or a non-empty 1-D array")
+        if y.size > 1 and sample_dt is None:
+            raise ValueError("sample_dt must be given with a sampled target")
+        x0 = None if x0 is None else self._start_states(x0)
+        final, metrics = self.sweep().score(self.trains, y, 1.0 if sample_dt is None else float(sample_dt), x0=x0)
+        inverse = np.empty(self.batch, dtype=np.int64)
+        inverse[self.order] = np.arange(self.batch)
+        result = {name: final[i, inverse].copy() for i, name in enumerate(self.model.name_dof)}
+        for i, name in enumerate(_cfx.SWEEP_METRICS):
+            result[name] = metrics[i, inverse].copy()
+        result["peak_node"] = result["peak_node"].astype(np.int64)
         return result
 
     def close(self):

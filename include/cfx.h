@@ -658,7 +658,26 @@ void cfx_ipm_destroy(cfx_ipm *s);
    responsible for them, the call is asynchronous on `hip_stream` (NULL = the HIP null stream) and nothing is copied.
    An instance's result does not depend on its position in the batch.
    cfx_sweep_check: the same argument checks without a device (trains == NULL: the creation arguments only); message
-   through cfx_last_error(NULL), as are cfx_sweep_create's. */
+   through cfx_last_error(NULL), as are cfx_sweep_create's.
+   cfx_sweep_score: the same rollout, scored on the device against a target force shared by the batch; no node
+   trajectory is written.  Target y(t): piecewise linear through n_samples values at t = j * sample_dt, the last one
+   held beyond the table:  u = t * (1.0 / sample_dt), j = (int)floor(u);  n_samples == 1 or j >= n_samples - 1:
+   y = y[n_samples - 1];  otherwise y = fma(u - j, y[j+1] - y[j], y[j]).  For instance b with N = n_shooting[b],
+   dt = final_time[b] / N, t_k = k * dt and F_k the force at node k = 0..N (F_0 from x0), metrics
+   [CFX_SWEEP_N_METRICS][B] holds, by row:
+     0 track       dt sum_{k=0..N} (F_k - y(t_k))^2
+     1 impulse     dt (F_0 / 2 + sum_{k=1..N-1} F_k + F_N / 2)
+     2 peak        max_k F_k
+     3 peak_node   the first k that attains the peak, as a double
+     4 end_error   F_N - y(t_N)
+     5 mean_force  impulse / final_time[b]
+   The sums run sequentially in k inside the instance's own thread (no atomics), so the metrics do not depend on
+   the instance's position either.  final_state [nx][B] has cfx_sweep_integrate's bits; x0, CFX_DEVICE and hip_stream
+   as there, and with CFX_DEVICE target->y is a device pointer too.  n_samples >= 1 and sample_dt > 0 are always
+   checked, a host target's samples (finite) with the host checks of the trains: a violation returns CFX_EINVAL with
+   nothing launched and the outputs untouched.  NULL target, metrics or final_state: CFX_EINVAL.
+   cfx_sweep_target_check: the checks of a host target alone, without a device; message through
+   cfx_last_error(NULL). */
 typedef struct cfx_sweep cfx_sweep;
 typedef struct cfx_sweep_trains {
     const double *times;
@@ -673,6 +692,15 @@ int cfx_sweep_check(int32_t model, int32_t scheme, int32_t n_steps, int64_t batc
                     int32_t max_shooting, const cfx_sweep_trains *trains);
 int cfx_sweep_integrate(cfx_sweep *s, const cfx_sweep_trains *trains, const double *x0, double *final_state,
                         double *nodes, uint32_t flags, void *hip_stream);
+typedef struct cfx_sweep_target { /* shared by the batch */
+    const double *y;              /* n_samples values of the target force at t = j * sample_dt */
+    int32_t n_samples;            /* >= 1 */
+    double sample_dt;             /* > 0; ignored when n_samples == 1 */
+} cfx_sweep_target;
+#define CFX_SWEEP_N_METRICS 6
+int cfx_sweep_score(cfx_sweep *s, const cfx_sweep_trains *trains, const cfx_sweep_target *target, const double *x0,
+                    double *final_state, double *metrics, uint32_t flags, void *hip_stream);
+int cfx_sweep_target_check(const cfx_sweep_target *target);
 const char *cfx_sweep_last_error(const cfx_sweep *s);
 void cfx_sweep_destroy(cfx_sweep *s);
 
