@@ -384,7 +384,30 @@ def _objective_array(objectives, keep, n_shooting):
     return objs
 
 
-class Handle:
+def _constants(values: dict):
+    """cfx_constants from a dict of model constants (one that is missing is 0)."""
+    cst = Constants()
+    for name, _ in Constants._fields_:
+        setattr(cst, name, float(values.get(name, 0.0)))
+    return cst
+
+
+class _Owner:
+    """close / __del__ of a wrapper that owns the library object ``self.h``; ``_DESTROY``: its destroy entry point."""
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.lib, self._DESTROY)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Handle(_Owner):
     """One libcfx handle: a batch of B instances of one transcribed FES problem on one GPU.
 
     Host numpy arrays are copied to the GPU and back synchronously; torch CUDA tensors (float64,
@@ -392,6 +415,7 @@ class Handle:
     """
 
     scheme = None  # the transcription (RK1 / RK2 / RK4 / COLLOCATION_*), set by _attach for every constructor
+    _DESTROY = "cfx_destroy"
 
     def __init__(self, *, model_id, constants: dict, scheme, n_steps, n_shooting, truncation, final_time,
                  stim_rows, batch, layout=LAYOUT_SOA, n_params=0, last_stim_idx=None, intensity_floor=0.0,
@@ -417,10 +441,7 @@ class Handle:
             self._keep.append(li)
             pb.last_stim_idx = li.ctypes.data_as(C.POINTER(C.c_int32))
         pb.intensity_floor = intensity_floor
-        cst = Constants()
-        for name, _ in Constants._fields_:
-            setattr(cst, name, float(constants.get(name, 0.0)))
-        pb.constants = cst
+        pb.constants = _constants(constants)
         objs = _objective_array(objectives, self._keep, n_shooting)
         pb.n_objectives = len(objectives)
         pb.objectives = objs
@@ -443,17 +464,6 @@ class Handle:
     def _check(self, rc):
         if rc != OK:
             raise CfxError(rc, self.lib.cfx_last_error(self.h).decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.cfx_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def launch_shape(self) -> dict:
         """The g + J_g kernels' launch shape fixed at creation (cfx_get_launch_shape)."""
@@ -759,10 +769,7 @@ class MskHandle(Handle):
         mus = (MskMuscle * len(muscles))()
         for i, m in enumerate(muscles):
             mus[i].model = m["model_id"]
-            cst = Constants()
-            for name, _ in Constants._fields_:
-                setattr(cst, name, float(m["constants"].get(name, 0.0)))
-            mus[i].constants = cst
+            mus[i].constants = _constants(m["constants"])
             mus[i].n_points = len(m["point_frame"])
             mus[i].point_frame = arr(m["point_frame"], np.int32)
             mus[i].point_pos = arr(m["point_pos"])
@@ -952,32 +959,47 @@ class Ipm:
             pass
 
 
-_SWEEP_FIELDS = (("times", "float64", True), ("act_node", "int32", True), ("value", "float64", True),
-                 ("n_pulses", "int32", False), ("truncation", "int32", False), ("n_shooting", "int32", False),
-                 ("final_time", "float64", False))
+# the arrays of cfx_sweep_trains and, with target and weight, of cfx_idm_trains: name, dtype, shape kind
+_TRAIN_FIELDS = (("times", "float64", "pulse"), ("act_node", "int32", "pulse"), ("value", "float64", "pulse"),
+                 ("n_pulses", "int32", "train"), ("truncation", "int32", "train"), ("n_shooting", "int32", "train"),
+                 ("final_time", "float64", "train"), ("target", "float64", "node"), ("weight", "float64", "node"))
 
 
-def _sweep_trains(trains: dict, batch, max_pulses, needs_value, device=None):
-    """cfx_sweep_trains over C-contiguous numpy arrays (device None) or CUDA tensors: (P, B) per-pulse arrays, (B,)
-    per-instance arrays.  Returns (struct, arrays kept alive)."""
-    st, keep = SweepTrains(), []
-    for name, dtype, per_pulse in _SWEEP_FIELDS:
+def _train_struct(label, st, shapes: dict, trains: dict, needs_value, device):
+    """Fills the train struct ``st`` with the arrays of ``trains`` whose shape kind ``shapes`` knows: C-contiguous
+    numpy arrays (device None) or CUDA tensors.  ``value`` (unless ``needs_value``) and the node arrays may be left
+    out.  Returns (struct, arrays kept alive)."""
+    keep = []
+    for name, dtype, kind in _TRAIN_FIELDS:
+        if kind not in shapes:
+            continue
         a = trains.get(name)
         if a is None:
-            if name == "value" and not needs_value:
+            if (name == "value" and not needs_value) or kind == "node":
                 continue
-            raise CfxError(EINVAL, f"sweep: trains[{name!r}] is missing")
-        shape = (max_pulses, batch) if per_pulse else (batch,)
+            raise CfxError(EINVAL, f"{label}: trains[{name!r}] is missing")
         if device is None:
             a = np.ascontiguousarray(a, dtype=dtype)
         elif not (_is_tensor(a) and a.is_cuda and a.device.index == device and a.is_contiguous()
                   and str(a.dtype) == "torch." + dtype):
-            raise CfxError(EINVAL, f"sweep: trains[{name!r}] must be a contiguous {dtype} tensor on cuda:{device}")
-        if tuple(a.shape) != shape:
-            raise CfxError(EINVAL, f"sweep: trains[{name!r}] must have shape {shape}, not {tuple(a.shape)}")
+            raise CfxError(EINVAL, f"{label}: trains[{name!r}] must be a contiguous {dtype} tensor on cuda:{device}")
+        if tuple(a.shape) != shapes[kind]:
+            raise CfxError(EINVAL, f"{label}: trains[{name!r}] must have shape {shapes[kind]}, not {tuple(a.shape)}")
         keep.append(a)
         setattr(st, name, _ptr(a))
     return st, keep
+
+
+def _sweep_trains(trains: dict, batch, max_pulses, needs_value, device=None):
+    """cfx_sweep_trains: (P, B) per-pulse arrays, (B,) per-instance arrays."""
+    return _train_struct("sweep", SweepTrains(), {"pulse": (max_pulses, batch), "train": (batch,)}, trains,
+                         needs_value, device)
+
+
+def _idm_trains(trains: dict, n_trains, max_pulses, max_shooting, needs_value, device=None):
+    """cfx_idm_trains: (P, E) per-pulse arrays, (E,) per-train arrays, (max_shooting + 1, E) target and weight."""
+    shapes = {"pulse": (max_pulses, n_trains), "train": (n_trains,), "node": (max_shooting + 1, n_trains)}
+    return _train_struct("idm", IdmTrains(), shapes, trains, needs_value, device)
 
 
 def sweep_check(model_id, scheme, n_steps, batch, max_pulses, max_shooting, trains: dict | None = None):
@@ -1005,19 +1027,18 @@ def sweep_target_check(target, sample_dt):
         raise CfxError(rc, lib.cfx_last_error(None).decode())
 
 
-class Sweep:
+class Sweep(_Owner):
     """One cfx_sweep: single shooting of B instances of one model, every instance with its own stimulation train
     (``trains``: the arrays of ``cfx_sweep_trains``, SoA).  Host numpy arrays are checked, copied and the call
     returns when the results are back; CUDA tensors are used in place, unchecked, on torch's current stream."""
 
+    _DESTROY = "cfx_sweep_destroy"
+
     def __init__(self, *, model_id, constants: dict, scheme, n_steps, batch, max_pulses, max_shooting, device=0):
         self.lib = load_library()
-        cst = Constants()
-        for name, _ in Constants._fields_:
-            setattr(cst, name, float(constants.get(name, 0.0)))
         h = C.c_void_p()
-        rc = self.lib.cfx_sweep_create(model_id, C.byref(cst), scheme, n_steps, batch, max_pulses, max_shooting,
-                                       device, C.byref(h))
+        rc = self.lib.cfx_sweep_create(model_id, C.byref(_constants(constants)), scheme, n_steps, batch, max_pulses,
+                                       max_shooting, device, C.byref(h))
         if rc != OK:
             raise CfxError(rc, self.lib.cfx_last_error(None).decode())
         self.h = h
@@ -1026,9 +1047,8 @@ class Sweep:
         self.nx = 5 if model_id & 1 else 2
         self.needs_value = model_id >= MODEL_IDS["ding2007"]
 
-    def integrate(self, trains: dict, x0=None, nodes=False):
-        """Final states (nx, B) and, with ``nodes``, the node states (max_shooting + 1, nx, B) (NaN past an
-        instance's own n_shooting); ``x0``: (nx, B) or None (the rest state).  Returns (final, nodes or None)."""
+    def _begin(self, trains, x0):
+        """(struct, kept arrays, x0, new(shape), stream, flags) of one call."""
         B, nx = self.batch, self.nx
         on_device = _is_tensor(trains.get("times"))
         st, keep = _sweep_trains(trains, B, self.max_pulses, self.needs_value, self.device if on_device else None)
@@ -1039,96 +1059,49 @@ class Sweep:
             if x0 is not None and not (_is_tensor(x0) and x0.is_cuda and x0.dtype == torch.float64
                                        and x0.is_contiguous() and tuple(x0.shape) == (nx, B)):
                 raise CfxError(EINVAL, f"sweep: x0 must be a contiguous float64 ({nx}, {B}) tensor on {dev}")
-            final = torch.empty((nx, B), dtype=torch.float64, device=dev)
-            out = torch.empty((self.max_shooting + 1, nx, B), dtype=torch.float64, device=dev) if nodes else None
+            new = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)  # noqa: E731
             stream, fl = torch.cuda.current_stream().cuda_stream, DEVICE
         else:
             if x0 is not None:
                 x0 = np.ascontiguousarray(x0, dtype=np.float64)
                 if x0.shape != (nx, B):
                     raise CfxError(EINVAL, f"sweep: x0 must have shape ({nx}, {B}), not {x0.shape}")
-            final = np.empty((nx, B))
-            out = np.empty((self.max_shooting + 1, nx, B)) if nodes else None
+            new = lambda *sh: np.empty(sh)  # noqa: E731
             stream, fl = None, 0
-        rc = self.lib.cfx_sweep_integrate(self.h, C.byref(st), _ptr(x0), _ptr(final), _ptr(out), fl, stream)
+        return st, keep, x0, new, stream, fl
+
+    def _check(self, rc):
         if rc != OK:
             raise CfxError(rc, self.lib.cfx_sweep_last_error(self.h).decode())
+
+    def integrate(self, trains: dict, x0=None, nodes=False):
+        """Final states (nx, B) and, with ``nodes``, the node states (max_shooting + 1, nx, B) (NaN past an
+        instance's own n_shooting); ``x0``: (nx, B) or None (the rest state).  Returns (final, nodes or None)."""
+        st, keep, x0, new, stream, fl = self._begin(trains, x0)
+        final = new(self.nx, self.batch)
+        out = new(self.max_shooting + 1, self.nx, self.batch) if nodes else None
+        self._check(self.lib.cfx_sweep_integrate(self.h, C.byref(st), _ptr(x0), _ptr(final), _ptr(out), fl, stream))
         return final, out
 
     def score(self, trains: dict, target, sample_dt, x0=None):
         """cfx_sweep_score: final states (nx, B) and the metrics (len(SWEEP_METRICS), B) of every instance's node
         forces against the target force ``target`` ((n_samples,) values at t = j ``sample_dt``; piecewise linear,
         the last sample held).  numpy arrays, or CUDA tensors throughout (``target`` too).  Returns (final, metrics)."""
-        B, nx, nm = self.batch, self.nx, len(SWEEP_METRICS)
-        on_device = _is_tensor(trains.get("times"))
-        st, keep = _sweep_trains(trains, B, self.max_pulses, self.needs_value, self.device if on_device else None)
-        if on_device:
-            import torch
-
-            dev = f"cuda:{self.device}"
-            if x0 is not None and not (_is_tensor(x0) and x0.is_cuda and x0.dtype == torch.float64
-                                       and x0.is_contiguous() and tuple(x0.shape) == (nx, B)):
-                raise CfxError(EINVAL, f"sweep: x0 must be a contiguous float64 ({nx}, {B}) tensor on {dev}")
+        st, keep, x0, new, stream, fl = self._begin(trains, x0)
+        if fl == DEVICE:
             if not (_is_tensor(target) and target.is_cuda and target.device.index == self.device
-                    and target.dtype == torch.float64 and target.is_contiguous() and target.dim() == 1):
-                raise CfxError(EINVAL, f"sweep: target must be a contiguous 1-D float64 tensor on {dev}")
-            final = torch.empty((nx, B), dtype=torch.float64, device=dev)
-            metrics = torch.empty((nm, B), dtype=torch.float64, device=dev)
-            stream, fl = torch.cuda.current_stream().cuda_stream, DEVICE
+                    and str(target.dtype) == "torch.float64" and target.is_contiguous() and target.dim() == 1):
+                raise CfxError(EINVAL, f"sweep: target must be a contiguous 1-D float64 tensor on cuda:{self.device}")
         else:
-            if x0 is not None:
-                x0 = np.ascontiguousarray(x0, dtype=np.float64)
-                if x0.shape != (nx, B):
-                    raise CfxError(EINVAL, f"sweep: x0 must have shape ({nx}, {B}), not {x0.shape}")
             target = np.ascontiguousarray(target, dtype=np.float64)
             if target.ndim != 1:
                 raise CfxError(EINVAL, "sweep: target must be 1-D")
-            final = np.empty((nx, B))
-            metrics = np.empty((nm, B))
-            stream, fl = None, 0
+        final = new(self.nx, self.batch)
+        metrics = new(len(SWEEP_METRICS), self.batch)
         tg = SweepTarget(_ptr(target), int(target.shape[0]), float(sample_dt))
-        rc = self.lib.cfx_sweep_score(self.h, C.byref(st), C.byref(tg), _ptr(x0), _ptr(final), _ptr(metrics), fl,
-                                      stream)
-        if rc != OK:
-            raise CfxError(rc, self.lib.cfx_sweep_last_error(self.h).decode())
+        self._check(self.lib.cfx_sweep_score(self.h, C.byref(st), C.byref(tg), _ptr(x0), _ptr(final), _ptr(metrics),
+                                             fl, stream))
         return final, metrics
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.cfx_sweep_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-_IDM_FIELDS = _SWEEP_FIELDS + (("target", "float64", None), ("weight", "float64", None))
-
-
-def _idm_trains(trains: dict, n_trains, max_pulses, max_shooting, needs_value, device=None):
-    """cfx_idm_trains over C-contiguous numpy arrays (device None) or CUDA tensors: (P, E) per-pulse arrays, (E,)
-    per-train arrays, (max_shooting + 1, E) target and weight (optional here).  Returns (struct, arrays kept alive)."""
-    st, keep = IdmTrains(), []
-    for name, dtype, kind in _IDM_FIELDS:
-        a = trains.get(name)
-        if a is None:
-            if (name == "value" and not needs_value) or kind is None:
-                continue
-            raise CfxError(EINVAL, f"idm: trains[{name!r}] is missing")
-        shape = {True: (max_pulses, n_trains), False: (n_trains,), None: (max_shooting + 1, n_trains)}[kind]
-        if device is None:
-            a = np.ascontiguousarray(a, dtype=dtype)
-        elif not (_is_tensor(a) and a.is_cuda and a.device.index == device and a.is_contiguous()
-                  and str(a.dtype) == "torch." + dtype):
-            raise CfxError(EINVAL, f"idm: trains[{name!r}] must be a contiguous {dtype} tensor on cuda:{device}")
-        if tuple(a.shape) != shape:
-            raise CfxError(EINVAL, f"idm: trains[{name!r}] must have shape {shape}, not {tuple(a.shape)}")
-        keep.append(a)
-        setattr(st, name, _ptr(a))
-    return st, keep
 
 
 def _idm_ids(param_ids):
@@ -1158,13 +1131,14 @@ def idfm_check(model_id, scheme, n_steps, batch, n_trains, max_pulses, max_shoot
               prefix="cfx_idfm")
 
 
-class Idm:
+class Idm(_Owner):
     """One cfx_idm: B starts x E stimulation trains that share the identified parameters of every start
     (``trains``: the arrays of ``cfx_idm_trains``, SoA with the train as the minor index).  Host numpy arrays are
     checked, copied and the call returns when the results are back; with a CUDA ``theta`` every array must be a CUDA
     tensor: used in place, unchecked, on torch's current stream."""
 
     _PREFIX = "cfx_idm"  # the entry points' family
+    _DESTROY = "cfx_idm_destroy"
 
     def _fn(self, name):
         return getattr(self.lib, f"{self._PREFIX}_{name}")
@@ -1172,12 +1146,9 @@ class Idm:
     def __init__(self, *, model_id, constants: dict, scheme, n_steps, batch, n_trains, max_pulses, max_shooting,
                  device=0):
         self.lib = load_library()
-        cst = Constants()
-        for name, _ in Constants._fields_:
-            setattr(cst, name, float(constants.get(name, 0.0)))
         h = C.c_void_p()
-        rc = self._fn("create")(model_id, C.byref(cst), scheme, n_steps, batch, n_trains, max_pulses,
-                                max_shooting, device, C.byref(h))
+        rc = self._fn("create")(model_id, C.byref(_constants(constants)), scheme, n_steps, batch, n_trains,
+                                max_pulses, max_shooting, device, C.byref(h))
         if rc != OK:
             raise CfxError(rc, self.lib.cfx_last_error(None).decode())
         self.h = h
@@ -1237,20 +1208,10 @@ class Idm:
                                        _ptr(gn), _ptr(cpt), fl, stream))
         return cost, grad, gn, cpt
 
-    def close(self):
-        if getattr(self, "h", None):
-            self._fn("destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class Idfm(Idm):
     """One cfx_idfm: ``Idm`` for a fatigue model, whose identified parameters are the fatigue parameters
     (``FATIGUE_PARAM_IDS``); same arrays, same calls."""
 
     _PREFIX = "cfx_idfm"
+    _DESTROY = "cfx_idfm_destroy"

@@ -1,5 +1,6 @@
 // cfx_api.hip — the C ABI of libcfx (include/cfx.h): problem set-up on the host, stimulation
-// coefficient tables, sparsity, buffer staging, and the launches of the gfx950 kernels.
+// coefficient tables, sparsity, buffer staging, and the launches of the gfx950 kernels.  The stimulation-train
+// families (cfx_sweep_*, cfx_idm_*, cfx_idfm_*) are in cfx_api_trains.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,12 +16,9 @@
 #include "cfx_colloc_ivp.h"
 #include "cfx_ident.h"
 #include "cfx_identf.h"
-#include "cfx_idfm.h"
-#include "cfx_idm.h"
 #include "cfx_internal.h"
 #include "cfx_launch.h"
 #include "cfx_msk_launch.h"
-#include "cfx_sweep.h"
 
 using namespace cfx;
 
@@ -30,11 +28,6 @@ thread_local std::string g_create_error;
 namespace {
 
 enum Slot { S_V = 0, S_A1, S_A2, S_G, S_J, S_F, S_GRAD, S_OUT, S_WORK, S_COUNT };
-
-struct DevBuf {
-    double* p = nullptr;
-    size_t n = 0;
-};
 
 }  // namespace
 
@@ -1252,7 +1245,7 @@ static int id_slot(int model, int pid) {
 }
 
 // The parameter-list checks; col[slot] = column of the slot in theta (-1: not identified).
-static int id_check(int model, int32_t n_id, const int32_t* ids, int32_t* col, std::string& msg) {
+int id_check(int model, int32_t n_id, const int32_t* ids, int32_t* col, std::string& msg) {
     if (model < CFX_DING2003 || model > CFX_HMED2018_FATIGUE) {
         msg = "cfx_id: unknown model";
         return CFX_EINVAL;
@@ -1541,7 +1534,7 @@ extern "C" int cfx_id_normal(cfx_handle* h, int32_t n_id, const int32_t* param_i
 // ------------------------------------------------------------------------------------------------------
 // The parameter-list checks; col[slot] = column of the slot in theta (-1: not identified).  The CFX_FP_* ids are
 // the direction slots.
-static int idf_check(int model, int32_t n_id, const int32_t* ids, int32_t* col, std::string& msg) {
+int idf_check(int model, int32_t n_id, const int32_t* ids, int32_t* col, std::string& msg) {
     if (model < CFX_DING2003 || model > CFX_HMED2018_FATIGUE) {
         msg = "cfx_idf: unknown model";
         return CFX_EINVAL;
@@ -2309,293 +2302,6 @@ __global__ void __launch_bounds__(256) k_gather_sum(int64_t batch, int64_t n_dst
     dst[b * n_dst + i] = acc;
 }
 
-// ------------------------------------------------------------------------------------------------------
-// stimulation-train sweeps (cfx_sweep.h): every instance carries its own train
-// ------------------------------------------------------------------------------------------------------
-struct cfx_sweep {
-    int model = 0, scheme = 1, nx = 2, device = 0;
-    int64_t B = 0;
-    int32_t P = 0, Nmax = 0, m = 1;
-    bool needs_value = false;
-    SweepParams sp{};
-    hipStream_t stream = nullptr;
-    // staging of host calls: times, value, final_time, x0, xf, nodes, target, metrics (doubles); act + the three
-    // counts (int32)
-    DevBuf dbuf[8];
-    int32_t* d_int = nullptr;
-    std::string err;
-};
-
-// The argument checks of cfx_sweep_create and (tr != nullptr) of the host arrays of cfx_sweep_integrate.
-static int sweep_check(const char* fn, int model, int scheme, int n_steps, int64_t B, int P, int Nmax,
-                       const cfx_sweep_trains* tr, std::string& msg) {
-    const std::string f = std::string(fn) + ": ";
-    if (model < CFX_DING2003 || model > CFX_HMED2018_FATIGUE) return msg = f + "unknown model", CFX_EINVAL;
-    if (scheme != CFX_RK1 && scheme != CFX_RK2 && scheme != CFX_RK4)
-        return msg = f + "unknown scheme (must be CFX_RK1, CFX_RK2 or CFX_RK4)", CFX_EINVAL;
-    if (n_steps < 1 || B < 1 || P < 1 || Nmax < 1)
-        return msg = f + "n_steps, batch, max_pulses and max_shooting must be positive", CFX_EINVAL;
-    if (Nmax > kMaxGridY) return msg = f + "max_shooting must be <= 65535", CFX_EINVAL;
-    if (!tr) return CFX_OK;
-    const bool needs_value = is_pw(model) || is_int(model);
-    if (!tr->times || !tr->act_node || !tr->n_pulses || !tr->truncation || !tr->n_shooting || !tr->final_time ||
-        (needs_value && !tr->value))
-        return msg = f + "a train array is NULL", CFX_EINVAL;
-    for (int64_t b = 0; b < B; ++b) {
-        const std::string at = f + "instance " + std::to_string(b) + ": ";
-        const int N = tr->n_shooting[b], np = tr->n_pulses[b];
-        if (N > kMaxGridY) return msg = at + "n_shooting must be <= 65535", CFX_EINVAL;
-        if (N < 1 || N > Nmax) return msg = at + "n_shooting must be in [1, max_shooting]", CFX_EINVAL;
-        if (tr->truncation[b] < 1) return msg = at + "truncation must be >= 1", CFX_EINVAL;
-        if (np < 0 || np > P) return msg = at + "n_pulses must be in [0, max_pulses]", CFX_EINVAL;
-        if (!(tr->final_time[b] > 0.0) || !std::isfinite(tr->final_time[b]))
-            return msg = at + "final_time must be positive and finite", CFX_EINVAL;
-        for (int i = 0; i < np; ++i) {
-            const std::string pi = at + "pulse " + std::to_string(i) + ": ";
-            const double t = tr->times[(int64_t)i * B + b];
-            const int a = tr->act_node[(int64_t)i * B + b];
-            if (!std::isfinite(t)) return msg = pi + "time is not finite", CFX_EINVAL;
-            if (i > 0 && t < tr->times[(int64_t)(i - 1) * B + b]) return msg = pi + "time decreases", CFX_EINVAL;
-            if (a < 0) return msg = pi + "activation node is negative", CFX_EINVAL;
-            if (a > N) return msg = pi + "activation node past n_shooting", CFX_EINVAL;
-            if (i > 0 && a < tr->act_node[(int64_t)(i - 1) * B + b])
-                return msg = pi + "activation node decreases", CFX_EINVAL;
-            if (needs_value && !std::isfinite(tr->value[(int64_t)i * B + b]))
-                return msg = pi + "value is not finite", CFX_EINVAL;
-        }
-    }
-    return CFX_OK;
-}
-
-extern "C" int cfx_sweep_check(int32_t model, int32_t scheme, int32_t n_steps, int64_t batch, int32_t max_pulses,
-                               int32_t max_shooting, const cfx_sweep_trains* trains) {
-    return sweep_check("cfx_sweep_check", model, scheme, n_steps, batch, max_pulses, max_shooting, trains,
-                       g_create_error);
-}
-
-extern "C" void cfx_sweep_destroy(cfx_sweep* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (DevBuf& b : s->dbuf)
-        if (b.p) (void)hipFree(b.p);
-    if (s->d_int) (void)hipFree(s->d_int);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
-}
-
-extern "C" const char* cfx_sweep_last_error(const cfx_sweep* s) { return s ? s->err.c_str() : g_create_error.c_str(); }
-
-extern "C" int cfx_sweep_create(int32_t model, const cfx_constants* c, int32_t scheme, int32_t n_steps, int64_t batch,
-                                int32_t max_pulses, int32_t max_shooting, int32_t device, cfx_sweep** out) {
-    if (!c || !out) return g_create_error = "cfx_sweep_create: NULL argument", CFX_EINVAL;
-    *out = nullptr;
-    int rc = sweep_check("cfx_sweep_create", model, scheme, n_steps, batch, max_pulses, max_shooting, nullptr,
-                         g_create_error);
-    if (rc != CFX_OK) return rc;
-    if (!(c->tauc > 0.0)) return g_create_error = "cfx_sweep_create: tauc must be positive", CFX_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return g_create_error = "cfx_sweep_create: no HIP device available (libcfx has no CPU path)", CFX_ENODEV;
-    if (device < 0 || device >= ndev) return g_create_error = "cfx_sweep_create: bad device ordinal", CFX_ENODEV;
-    cfx_sweep* s = new cfx_sweep();
-    s->model = model;
-    s->scheme = scheme;
-    s->nx = is_fatigue(model) ? 5 : 2;
-    s->device = device;
-    s->B = batch;
-    s->P = max_pulses;
-    s->Nmax = max_shooting;
-    s->m = n_steps;
-    s->needs_value = is_pw(model) || is_int(model);
-    SweepParams& sp = s->sp;
-    sp.B = batch;
-    sp.P = max_pulses;
-    sp.Nmax = max_shooting;
-    sp.m = n_steps;
-    sp.inv_tauc = 1.0 / c->tauc;
-    sp.r0m1 = c->km_rest + c->r0_km_relationship - 1.0;
-    sp.mult = c->fl * c->fv + c->fp;
-    sp.tau2 = c->tau2;
-    sp.a_rest = is_pw(model) ? c->a_scale : c->a_rest;
-    sp.tau1_rest = c->tau1_rest;
-    sp.km_rest = c->km_rest;
-    sp.pd0 = c->pd0;
-    sp.inv_pdt = is_pw(model) ? 1.0 / c->pdt : 0.0;
-    sp.ar = c->ar;
-    sp.bs = c->bs;
-    sp.Is = c->Is;
-    sp.cr = c->cr;
-    sp.alpha_a = c->alpha_a;
-    sp.alpha_tau1 = c->alpha_tau1;
-    sp.alpha_km = c->alpha_km;
-    sp.inv_tau_fat = is_fatigue(model) ? 1.0 / c->tau_fat : 0.0;
-    if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
-        s->stream = nullptr;
-        cfx_sweep_destroy(s);
-        return g_create_error = "cfx_sweep_create: could not create a stream on the device", CFX_EHIP;
-    }
-    *out = s;
-    return CFX_OK;
-}
-
-static int sweep_fail(cfx_sweep* s, int code, const std::string& msg) {
-    s->err = msg;
-    return code;
-}
-
-// device buffer `slot` of at least n doubles
-static double* sweep_buf(cfx_sweep* s, int slot, size_t n, int* rc) {
-    DevBuf& b = s->dbuf[slot];
-    if (b.n < n) {
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr;
-        b.n = 0;
-        if (hipMalloc(&b.p, n * sizeof(double)) != hipSuccess) {
-            b.p = nullptr;
-            *rc = sweep_fail(s, CFX_ENOMEM, "cfx_sweep_integrate: hipMalloc failed");
-            return nullptr;
-        }
-        b.n = n;
-    }
-    return b.p;
-}
-
-static_assert(kSweepMetrics == CFX_SWEEP_N_METRICS, "metric rows of k_sweep and of cfx.h differ");
-
-// The checks of a target force; host: the samples too (a device caller is responsible for them).
-static int sweep_target_check(const char* fn, const cfx_sweep_target* tg, bool host, std::string& msg) {
-    const std::string f = std::string(fn) + ": ";
-    if (!tg) return msg = f + "target is NULL", CFX_EINVAL;
-    if (tg->n_samples < 1) return msg = f + "target: n_samples must be >= 1", CFX_EINVAL;
-    if (tg->n_samples > 1 && !(tg->sample_dt > 0.0)) return msg = f + "target: sample_dt must be positive", CFX_EINVAL;
-    if (!tg->y) return msg = f + "target: y is NULL", CFX_EINVAL;
-    if (host)
-        for (int32_t j = 0; j < tg->n_samples; ++j)
-            if (!std::isfinite(tg->y[j]))
-                return msg = f + "target: y[" + std::to_string(j) + "] is not finite", CFX_EINVAL;
-    return CFX_OK;
-}
-
-extern "C" int cfx_sweep_target_check(const cfx_sweep_target* target) {
-    return sweep_target_check("cfx_sweep_target_check", target, true, g_create_error);
-}
-
-// cfx_sweep_integrate (tg == nullptr) and cfx_sweep_score (tg, metrics; no nodes): one staging path, one launch.
-static int sweep_run(const char* fn, cfx_sweep* s, const cfx_sweep_trains* tr, const cfx_sweep_target* tg,
-                     const double* x0, double* final_state, double* nodes, double* metrics, uint32_t flags,
-                     void* hip_stream) {
-    const std::string f = std::string(fn) + ": ";
-    if (!tr->times || !tr->act_node || !tr->n_pulses || !tr->truncation || !tr->n_shooting || !tr->final_time ||
-        (s->needs_value && !tr->value))
-        return sweep_fail(s, CFX_EINVAL, f + "a train array is NULL");
-    const size_t B = (size_t)s->B, P = (size_t)s->P, nx = (size_t)s->nx, nn = (size_t)s->Nmax + 1;
-    const size_t nt = tg ? (size_t)tg->n_samples : 0;
-    SweepParams sp = s->sp;
-    if (tg) {
-        sp.tn = tg->n_samples;
-        sp.inv_sdt = tg->n_samples > 1 ? 1.0 / tg->sample_dt : 1.0;
-    }
-    const auto launch = [&](hipStream_t st) {
-        return tg ? launch_sweep_score(s->model, s->scheme, sp, st) : launch_sweep(s->model, s->scheme, sp, st);
-    };
-    if (hipSetDevice(s->device) != hipSuccess) return sweep_fail(s, CFX_EHIP, f + "hipSetDevice failed");
-    if (flags & CFX_DEVICE) {
-        sp.times = tr->times;
-        sp.act = tr->act_node;
-        sp.value = tr->value;
-        sp.n_pulses = tr->n_pulses;
-        sp.truncation = tr->truncation;
-        sp.n_shooting = tr->n_shooting;
-        sp.final_time = tr->final_time;
-        sp.x0 = x0;
-        sp.xf = final_state;
-        sp.nodes = nodes;
-        if (tg) sp.ty = tg->y;
-        sp.metrics = metrics;
-        const hipError_t e = launch((hipStream_t)hip_stream);
-        if (e != hipSuccess) return sweep_fail(s, CFX_EHIP, f + hipGetErrorString(e));
-        return CFX_OK;
-    }
-    int rc = sweep_check(fn, s->model, s->scheme, s->m, s->B, s->P, s->Nmax, tr, s->err);
-    if (rc != CFX_OK) return rc;
-    if (tg && (rc = sweep_target_check(fn, tg, true, s->err)) != CFX_OK) return rc;
-    if (x0)
-        for (size_t i = 0; i < nx * B; ++i)
-            if (!std::isfinite(x0[i])) return sweep_fail(s, CFX_EINVAL, f + "x0 is not finite");
-    double* d_t = sweep_buf(s, 0, P * B, &rc);
-    double* d_v = s->needs_value ? sweep_buf(s, 1, P * B, &rc) : nullptr;
-    double* d_tf = sweep_buf(s, 2, B, &rc);
-    double* d_x0 = x0 ? sweep_buf(s, 3, nx * B, &rc) : nullptr;
-    double* d_xf = sweep_buf(s, 4, nx * B, &rc);
-    double* d_nd = nodes ? sweep_buf(s, 5, nn * nx * B, &rc) : nullptr;
-    double* d_ty = tg ? sweep_buf(s, 6, nt, &rc) : nullptr;
-    double* d_mt = tg ? sweep_buf(s, 7, (size_t)kSweepMetrics * B, &rc) : nullptr;
-    if (!d_t || (s->needs_value && !d_v) || !d_tf || (x0 && !d_x0) || !d_xf || (nodes && !d_nd) ||
-        (tg && (!d_ty || !d_mt)))
-        return rc;
-    if (!s->d_int && hipMalloc(&s->d_int, (P + 3) * B * sizeof(int32_t)) != hipSuccess) {
-        s->d_int = nullptr;
-        return sweep_fail(s, CFX_ENOMEM, f + "hipMalloc failed");
-    }
-    int32_t* d_act = s->d_int;
-    int32_t* d_cnt = s->d_int + P * B;
-    hipStream_t st = s->stream;
-#define SWEEP_HIP(call)                                                                          \
-    do {                                                                                         \
-        hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess) return sweep_fail(s, CFX_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-    SWEEP_HIP(hipMemcpyAsync(d_t, tr->times, P * B * sizeof(double), hipMemcpyHostToDevice, st));
-    if (d_v) SWEEP_HIP(hipMemcpyAsync(d_v, tr->value, P * B * sizeof(double), hipMemcpyHostToDevice, st));
-    SWEEP_HIP(hipMemcpyAsync(d_tf, tr->final_time, B * sizeof(double), hipMemcpyHostToDevice, st));
-    if (d_x0) SWEEP_HIP(hipMemcpyAsync(d_x0, x0, nx * B * sizeof(double), hipMemcpyHostToDevice, st));
-    if (d_ty) SWEEP_HIP(hipMemcpyAsync(d_ty, tg->y, nt * sizeof(double), hipMemcpyHostToDevice, st));
-    SWEEP_HIP(hipMemcpyAsync(d_act, tr->act_node, P * B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    SWEEP_HIP(hipMemcpyAsync(d_cnt, tr->n_pulses, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    SWEEP_HIP(hipMemcpyAsync(d_cnt + B, tr->truncation, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    SWEEP_HIP(hipMemcpyAsync(d_cnt + 2 * B, tr->n_shooting, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    sp.times = d_t;
-    sp.act = d_act;
-    sp.value = d_v;
-    sp.n_pulses = d_cnt;
-    sp.truncation = d_cnt + B;
-    sp.n_shooting = d_cnt + 2 * B;
-    sp.final_time = d_tf;
-    sp.x0 = d_x0;
-    sp.xf = d_xf;
-    sp.nodes = d_nd;
-    sp.ty = d_ty;
-    sp.metrics = d_mt;
-    SWEEP_HIP(launch(st));
-    SWEEP_HIP(hipMemcpyAsync(final_state, d_xf, nx * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (d_nd) SWEEP_HIP(hipMemcpyAsync(nodes, d_nd, nn * nx * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (d_mt)
-        SWEEP_HIP(hipMemcpyAsync(metrics, d_mt, (size_t)kSweepMetrics * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    SWEEP_HIP(hipStreamSynchronize(st));
-#undef SWEEP_HIP
-    return CFX_OK;
-}
-
-extern "C" int cfx_sweep_integrate(cfx_sweep* s, const cfx_sweep_trains* tr, const double* x0, double* final_state,
-                                   double* nodes, uint32_t flags, void* hip_stream) {
-    if (!s) return g_create_error = "cfx_sweep_integrate: NULL handle", CFX_EINVAL;
-    if (!tr || !final_state) return sweep_fail(s, CFX_EINVAL, "cfx_sweep_integrate: trains or final_state is NULL");
-    return sweep_run("cfx_sweep_integrate", s, tr, nullptr, x0, final_state, nodes, nullptr, flags, hip_stream);
-}
-
-extern "C" int cfx_sweep_score(cfx_sweep* s, const cfx_sweep_trains* tr, const cfx_sweep_target* tg, const double* x0,
-                               double* final_state, double* metrics, uint32_t flags, void* hip_stream) {
-    if (!s) return g_create_error = "cfx_sweep_score: NULL handle", CFX_EINVAL;
-    if (!tr || !tg || !final_state || !metrics)
-        return sweep_fail(s, CFX_EINVAL, "cfx_sweep_score: trains, target, final_state or metrics is NULL");
-    // n_samples and sample_dt are host values with CFX_DEVICE too
-    const int rc = sweep_target_check("cfx_sweep_score", tg, false, s->err);
-    if (rc != CFX_OK) return rc;
-    return sweep_run("cfx_sweep_score", s, tr, tg, x0, final_state, nullptr, metrics, flags, hip_stream);
-}
-
 extern "C" int cfx_gather_sum(int64_t batch, int64_t n_dst, const int32_t* ptr, const int32_t* idx, const double* src,
                               int64_t src_len, double* dst, void* stream) {
     if (batch < 1 || n_dst < 0 || src_len < 0 || !ptr || (n_dst && (!idx || !src || !dst)) || batch > kMaxGridY) {
@@ -2612,519 +2318,3 @@ extern "C" int cfx_gather_sum(int64_t batch, int64_t n_dst, const int32_t* ptr, 
     }
     return CFX_OK;
 }
-
-// ------------------------------------------------------------------------------------------------------
-// multi-train force-parameter identification (cfx_idm.h): E trains share the parameters of every start
-// ------------------------------------------------------------------------------------------------------
-struct cfx_idm {
-    int model = 0, scheme = 1, device = 0;
-    int64_t B = 0;
-    int32_t E = 0, P = 0, Nmax = 0, m = 1;
-    bool needs_value = false;
-    IdmParams ip{};
-    hipStream_t stream = nullptr;
-    double* d_ws = nullptr;  // [E][1 + 8 + 36][B]: the per-train normal equations (host and device calls)
-    // staging of host calls: times, value, final_time, target, weight, theta, force, sens, cost | grad | gn | cost_per_train
-    DevBuf dbuf[9];
-    int32_t* d_int = nullptr;  // act [P][E] + the three counts [E]
-    std::string err;
-};
-
-static const int kIdmRowsMax = 1 + CFX_ID_MAX_PARAMS + CFX_ID_MAX_PARAMS * (CFX_ID_MAX_PARAMS + 1) / 2;
-
-static int idm_check_trains(const char* fn, int model, int scheme, int n_steps, int64_t B, int E, int P, int Nmax,
-                            const cfx_idm_trains* tr, std::string& msg);
-
-// Every argument check of cfx_idm_create (ids == nullptr: no parameter list), cfx_idm_forces and cfx_idm_normal;
-// tr != nullptr: the host arrays too.  The train rules are cfx_sweep_check's with the train in the instance's place.
-static int idm_check(const char* fn, int model, int scheme, int n_steps, int64_t B, int E, int P, int Nmax,
-                     bool with_ids, int32_t n_id, const int32_t* ids, int32_t* col, const cfx_idm_trains* tr,
-                     std::string& msg) {
-    const std::string f = std::string(fn) + ": ";
-    if (model < CFX_DING2003 || model > CFX_HMED2018_FATIGUE) return msg = f + "unknown model", CFX_EINVAL;
-    if (is_fatigue(model))
-        return msg = f + "identification is not available for the fatigue models", CFX_EUNSUPPORTED;
-    if (E < 1) return msg = f + "n_trains must be positive", CFX_EINVAL;
-    if (E > kMaxGridY) return msg = f + "n_trains must be <= 65535", CFX_EINVAL;
-    if (with_ids) {
-        std::string m2;
-        const int rc = id_check(model, n_id, ids, col, m2);
-        if (rc != CFX_OK) return msg = std::string(fn) + m2.substr(6), rc;  // "cfx_id" -> the caller's name
-    }
-    return idm_check_trains(fn, model, scheme, n_steps, B, E, P, Nmax, tr, msg);
-}
-
-// The train rules (also cfx_idfm_*'s): cfx_sweep_check's with the train in the instance's place, then target and
-// weight.
-static int idm_check_trains(const char* fn, int model, int scheme, int n_steps, int64_t B, int E, int P, int Nmax,
-                            const cfx_idm_trains* tr, std::string& msg) {
-    const std::string f = std::string(fn) + ": ";
-    cfx_sweep_trains st{};
-    if (tr) {
-        st.times = tr->times;
-        st.act_node = tr->act_node;
-        st.value = tr->value;
-        st.n_pulses = tr->n_pulses;
-        st.truncation = tr->truncation;
-        st.n_shooting = tr->n_shooting;
-        st.final_time = tr->final_time;
-    }
-    // batch first (the sweep's "batch" below is the train count)
-    if (B < 1) return msg = f + "n_steps, batch, max_pulses and max_shooting must be positive", CFX_EINVAL;
-    int rc = sweep_check(fn, model, scheme, n_steps, E, P, Nmax, tr ? &st : nullptr, msg);
-    if (rc != CFX_OK) {
-        const size_t at = msg.find(": instance ");
-        if (at != std::string::npos) msg.replace(at + 2, 8, "train");
-        return rc;
-    }
-    if (!tr) return CFX_OK;
-    for (int pass = 0; pass < 2; ++pass) {
-        const double* a = pass == 0 ? tr->target : tr->weight;
-        if (!a) continue;
-        for (int e = 0; e < E; ++e)
-            for (int k = 0; k <= tr->n_shooting[e]; ++k) {
-                const double v = a[(int64_t)k * E + e];
-                if (!std::isfinite(v) || (pass == 1 && v < 0.0))
-                    return msg = f + "train " + std::to_string(e) + ": node " + std::to_string(k) +
-                                 (pass == 0 ? ": target is not finite" : ": weight must be finite and >= 0"),
-                           CFX_EINVAL;
-            }
-    }
-    return CFX_OK;
-}
-
-extern "C" int cfx_idm_check(int32_t model, int32_t scheme, int32_t n_steps, int64_t batch, int32_t n_trains,
-                             int32_t max_pulses, int32_t max_shooting, int32_t n_id, const int32_t* param_ids,
-                             const cfx_idm_trains* trains) {
-    int32_t col[ID_SLOTS];
-    return idm_check("cfx_idm_check", model, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, true, n_id,
-                     param_ids, col, trains, g_create_error);
-}
-
-extern "C" void cfx_idm_destroy(cfx_idm* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (DevBuf& b : s->dbuf)
-        if (b.p) (void)hipFree(b.p);
-    if (s->d_int) (void)hipFree(s->d_int);
-    if (s->d_ws) (void)hipFree(s->d_ws);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
-}
-
-extern "C" const char* cfx_idm_last_error(const cfx_idm* s) { return s ? s->err.c_str() : g_create_error.c_str(); }
-
-extern "C" int cfx_idm_create(int32_t model, const cfx_constants* c, int32_t scheme, int32_t n_steps, int64_t batch,
-                              int32_t n_trains, int32_t max_pulses, int32_t max_shooting, int32_t device,
-                              cfx_idm** out) {
-    if (!c || !out) return g_create_error = "cfx_idm_create: NULL argument", CFX_EINVAL;
-    *out = nullptr;
-    int rc = idm_check("cfx_idm_create", model, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, false, 0,
-                       nullptr, nullptr, nullptr, g_create_error);
-    if (rc != CFX_OK) return rc;
-    if (!(c->tauc > 0.0)) return g_create_error = "cfx_idm_create: tauc must be positive", CFX_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return g_create_error = "cfx_idm_create: no HIP device available (libcfx has no CPU path)", CFX_ENODEV;
-    if (device < 0 || device >= ndev) return g_create_error = "cfx_idm_create: bad device ordinal", CFX_ENODEV;
-    cfx_idm* s = new cfx_idm();
-    s->model = model;
-    s->scheme = scheme;
-    s->device = device;
-    s->B = batch;
-    s->E = n_trains;
-    s->P = max_pulses;
-    s->Nmax = max_shooting;
-    s->m = n_steps;
-    s->needs_value = is_pw(model) || is_int(model);
-    IdmParams& ip = s->ip;
-    ip.B = batch;
-    ip.E = n_trains;
-    ip.P = max_pulses;
-    ip.Nmax = max_shooting;
-    ip.m = n_steps;
-    ip.inv_tauc = 1.0 / c->tauc;
-    ip.mult = c->fl * c->fv + c->fp;
-    ip.r0_km = c->r0_km_relationship;
-    for (int k = 0; k < ID_SLOTS; ++k) ip.def[k] = 0.0;
-    ip.def[ID_A] = is_pw(model) ? c->a_scale : c->a_rest;
-    ip.def[ID_KM] = c->km_rest;
-    ip.def[ID_TAU1] = c->tau1_rest;
-    ip.def[ID_TAU2] = c->tau2;
-    if (is_pw(model)) {
-        ip.def[ID_P4] = c->pd0;
-        ip.def[ID_P5] = c->pdt;
-    }
-    if (is_int(model)) {
-        ip.def[ID_P4] = c->ar;
-        ip.def[ID_P5] = c->bs;
-        ip.def[ID_P6] = c->Is;
-        ip.def[ID_P7] = c->cr;
-    }
-    if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
-        s->stream = nullptr;
-        cfx_idm_destroy(s);
-        return g_create_error = "cfx_idm_create: could not create a stream on the device", CFX_EHIP;
-    }
-    if (hipMalloc((void**)&s->d_ws, (size_t)n_trains * kIdmRowsMax * (size_t)batch * sizeof(double)) != hipSuccess) {
-        s->d_ws = nullptr;
-        cfx_idm_destroy(s);
-        return g_create_error = "cfx_idm_create: hipMalloc of the workspace failed", CFX_ENOMEM;
-    }
-    *out = s;
-    return CFX_OK;
-}
-
-static int idm_fail(cfx_idm* s, int code, const std::string& msg) {
-    s->err = msg;
-    return code;
-}
-
-// device buffer `slot` of at least n doubles
-static double* idm_buf(cfx_idm* s, int slot, size_t n, int* rc) {
-    DevBuf& b = s->dbuf[slot];
-    if (b.n < n) {
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr;
-        b.n = 0;
-        if (hipMalloc(&b.p, n * sizeof(double)) != hipSuccess) {
-            b.p = nullptr;
-            *rc = idm_fail(s, CFX_ENOMEM, "cfx_idm: hipMalloc failed");
-            return nullptr;
-        }
-        b.n = n;
-    }
-    return b.p;
-}
-
-#define IDM_HIP(call)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e_ = (call);                                                                                \
-        if (e_ != hipSuccess) return idm_fail(s, CFX_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// The train rules and the parameter-list rules of a multi-train family: idm_check or idfm_check.
-typedef int (*IdmCheckFn)(const char* fn, int model, int scheme, int n_steps, int64_t B, int E, int P, int Nmax,
-                          bool with_ids, int32_t n_id, const int32_t* ids, int32_t* col, const cfx_idm_trains* tr,
-                          std::string& msg);
-
-// The device's view of the (checked) trains and of theta, written into the kernel parameters ip (IdmParams or
-// IdfmParams: the same nine train pointers): the caller's own pointers with CFX_DEVICE, else the handle's staging
-// buffers after the upload.  *TH: the device theta; *st: the stream to launch on.
-template <class Params>
-static int idm_stage(cfx_idm* s, const char* fn, const cfx_idm_trains* tr, bool normal, int32_t n_id,
-                     const double* theta, uint32_t flags, void* hip_stream, Params& ip, const double** TH,
-                     hipStream_t* st) {
-    const std::string f = std::string(fn) + ": ";
-    int rc = CFX_OK;
-    if (hipSetDevice(s->device) != hipSuccess) return idm_fail(s, CFX_EHIP, f + "hipSetDevice failed");
-    if ((flags & CFX_DEVICE) != 0) {
-        ip.times = tr->times;
-        ip.act = tr->act_node;
-        ip.value = tr->value;
-        ip.n_pulses = tr->n_pulses;
-        ip.truncation = tr->truncation;
-        ip.n_shooting = tr->n_shooting;
-        ip.final_time = tr->final_time;
-        ip.target = tr->target;
-        ip.weight = tr->weight;
-        *TH = theta;
-        *st = (hipStream_t)hip_stream;
-        return CFX_OK;
-    }
-    const size_t B = (size_t)s->B, E = (size_t)s->E, P = (size_t)s->P, nn = (size_t)s->Nmax + 1;
-    for (size_t i = 0; i < (size_t)n_id * B; ++i)
-        if (!std::isfinite(theta[i])) return idm_fail(s, CFX_EINVAL, f + "theta is not finite");
-    double* d_t = idm_buf(s, 0, P * E, &rc);
-    double* d_v = s->needs_value ? idm_buf(s, 1, P * E, &rc) : nullptr;
-    double* d_tf = idm_buf(s, 2, E, &rc);
-    double* d_y = normal ? idm_buf(s, 3, nn * E, &rc) : nullptr;
-    double* d_w = normal ? idm_buf(s, 4, nn * E, &rc) : nullptr;
-    double* d_th = idm_buf(s, 5, (size_t)CFX_ID_MAX_PARAMS * B, &rc);
-    if (!d_t || (s->needs_value && !d_v) || !d_tf || (normal && (!d_y || !d_w)) || !d_th) return rc;
-    if (!s->d_int && hipMalloc(&s->d_int, (P + 3) * E * sizeof(int32_t)) != hipSuccess) {
-        s->d_int = nullptr;
-        return idm_fail(s, CFX_ENOMEM, f + "hipMalloc failed");
-    }
-    int32_t* d_act = s->d_int;
-    int32_t* d_cnt = s->d_int + P * E;
-    hipStream_t q = s->stream;
-    IDM_HIP(hipMemcpyAsync(d_t, tr->times, P * E * sizeof(double), hipMemcpyHostToDevice, q));
-    if (d_v) IDM_HIP(hipMemcpyAsync(d_v, tr->value, P * E * sizeof(double), hipMemcpyHostToDevice, q));
-    IDM_HIP(hipMemcpyAsync(d_tf, tr->final_time, E * sizeof(double), hipMemcpyHostToDevice, q));
-    if (d_y) IDM_HIP(hipMemcpyAsync(d_y, tr->target, nn * E * sizeof(double), hipMemcpyHostToDevice, q));
-    if (d_w) IDM_HIP(hipMemcpyAsync(d_w, tr->weight, nn * E * sizeof(double), hipMemcpyHostToDevice, q));
-    IDM_HIP(hipMemcpyAsync(d_th, theta, (size_t)n_id * B * sizeof(double), hipMemcpyHostToDevice, q));
-    IDM_HIP(hipMemcpyAsync(d_act, tr->act_node, P * E * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    IDM_HIP(hipMemcpyAsync(d_cnt, tr->n_pulses, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    IDM_HIP(hipMemcpyAsync(d_cnt + E, tr->truncation, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    IDM_HIP(hipMemcpyAsync(d_cnt + 2 * E, tr->n_shooting, E * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    ip.times = d_t;
-    ip.act = d_act;
-    ip.value = d_v;
-    ip.n_pulses = d_cnt;
-    ip.truncation = d_cnt + E;
-    ip.n_shooting = d_cnt + 2 * E;
-    ip.final_time = d_tf;
-    ip.target = d_y;
-    ip.weight = d_w;
-    *TH = d_th;
-    *st = q;
-    return CFX_OK;
-}
-
-// What the forces and normal calls of both multi-train families do before the launch: the argument checks (check:
-// the family's rules), and for a host call the upload of the trains and of theta.  ip: the handle's parameters `base`
-// with this call's columns and trains; *TH the device theta; *st the stream to launch on.
-template <class Params>
-static int idm_begin(cfx_idm* s, const Params& base, IdmCheckFn check, const char* fn, const cfx_idm_trains* tr,
-                     bool normal, int32_t n_id, const int32_t* ids, const double* theta, uint32_t flags,
-                     void* hip_stream, Params& ip, const double** TH, hipStream_t* st) {
-    const std::string f = std::string(fn) + ": ";
-    if (!tr || !theta) return idm_fail(s, CFX_EINVAL, f + "trains or theta is NULL");
-    if (!tr->times || !tr->act_node || !tr->n_pulses || !tr->truncation || !tr->n_shooting || !tr->final_time ||
-        (s->needs_value && !tr->value))
-        return idm_fail(s, CFX_EINVAL, f + "a train array is NULL");
-    if (normal && (!tr->target || !tr->weight)) return idm_fail(s, CFX_EINVAL, f + "target or weight is NULL");
-    const bool dev = (flags & CFX_DEVICE) != 0;
-    constexpr int kSlots = (int)(sizeof(base.col) / sizeof(base.col[0]));
-    int32_t col[kSlots];
-    // with device arrays only the creation arguments and the parameter list can be checked here
-    const int rc = check(fn, s->model, s->scheme, s->m, s->B, s->E, s->P, s->Nmax, true, n_id, ids, col,
-                         dev ? nullptr : tr, s->err);
-    if (rc != CFX_OK) return rc;
-    ip = base;
-    ip.n_id = n_id;
-    for (int k = 0; k < kSlots; ++k) ip.col[k] = col[k];
-    return idm_stage(s, fn, tr, normal, n_id, theta, flags, hip_stream, ip, TH, st);
-}
-
-// What the forces calls of both families do around their launch: launch(F, S) (a CFX_* code) on the caller's arrays
-// with CFX_DEVICE, else on the handle's buffers, followed by the copies back and the synchronisation.
-template <class Launch>
-static int idm_forces_staged(cfx_idm* s, int32_t n_id, double* force, double* sens, uint32_t flags, hipStream_t st,
-                             Launch&& launch) {
-    int rc = CFX_OK;
-    if (flags & CFX_DEVICE) return launch(force, sens);
-    const size_t nf = (size_t)s->E * ((size_t)s->Nmax + 1) * (size_t)s->B, ns = nf * (size_t)n_id;
-    double* d_f = idm_buf(s, 6, nf, &rc);
-    double* d_s = sens ? idm_buf(s, 7, ns, &rc) : nullptr;
-    if (!d_f || (sens && !d_s)) return rc;
-    if ((rc = launch(d_f, d_s)) != CFX_OK) return rc;
-    IDM_HIP(hipMemcpyAsync(force, d_f, nf * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (d_s) IDM_HIP(hipMemcpyAsync(sens, d_s, ns * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipStreamSynchronize(st));
-    return CFX_OK;
-}
-
-// The same for the normal calls: launch(C, G, H, CPT).
-template <class Launch>
-static int idm_normal_staged(cfx_idm* s, int32_t n_id, double* cost, double* grad, double* gn, double* cost_per_train,
-                             uint32_t flags, hipStream_t st, Launch&& launch) {
-    int rc = CFX_OK;
-    if (flags & CFX_DEVICE) return launch(cost, grad, gn, cost_per_train);
-    const size_t B = (size_t)s->B, n = (size_t)n_id, npk = n * (n + 1) / 2, E = (size_t)s->E;
-    double* d_o = idm_buf(s, 8, (1 + n + npk + E) * B, &rc);
-    if (!d_o) return rc;
-    double *d_c = d_o, *d_g = d_o + B, *d_h = d_g + n * B, *d_p = cost_per_train ? d_h + npk * B : nullptr;
-    if ((rc = launch(d_c, d_g, d_h, d_p)) != CFX_OK) return rc;
-    IDM_HIP(hipMemcpyAsync(cost, d_c, B * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipMemcpyAsync(grad, d_g, n * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipMemcpyAsync(gn, d_h, npk * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (d_p) IDM_HIP(hipMemcpyAsync(cost_per_train, d_p, E * B * sizeof(double), hipMemcpyDeviceToHost, st));
-    IDM_HIP(hipStreamSynchronize(st));
-    return CFX_OK;
-}
-
-// slots 0..3 only: the 4-direction kernels
-static int idm_dirs(const IdmParams& ip) {
-    for (int k = 4; k < ID_SLOTS; ++k)
-        if (ip.col[k] >= 0) return 8;
-    return 4;
-}
-
-extern "C" int cfx_idm_forces(cfx_idm* s, const cfx_idm_trains* tr, int32_t n_id, const int32_t* param_ids,
-                              const double* theta, double* force, double* sens, uint32_t flags, void* hip_stream) {
-    if (!s) return g_create_error = "cfx_idm_forces: NULL handle", CFX_EINVAL;
-    if (!force) return idm_fail(s, CFX_EINVAL, "cfx_idm_forces: force is NULL");
-    IdmParams ip;
-    const double* TH = nullptr;
-    hipStream_t st = nullptr;
-    const int rc = idm_begin(s, s->ip, idm_check, "cfx_idm_forces", tr, false, n_id, param_ids, theta, flags,
-                             hip_stream, ip, &TH, &st);
-    if (rc != CFX_OK) return rc;
-    return idm_forces_staged(s, n_id, force, sens, flags, st, [&](double* F, double* S) -> int {
-        IDM_HIP(launch_idm_sens(s->model, s->scheme, idm_dirs(ip), ip, TH, F, S, st));
-        return CFX_OK;
-    });
-}
-
-extern "C" int cfx_idm_normal(cfx_idm* s, const cfx_idm_trains* tr, int32_t n_id, const int32_t* param_ids,
-                              const double* theta, double* cost, double* grad, double* gn, double* cost_per_train,
-                              uint32_t flags, void* hip_stream) {
-    if (!s) return g_create_error = "cfx_idm_normal: NULL handle", CFX_EINVAL;
-    if (!cost || !grad || !gn) return idm_fail(s, CFX_EINVAL, "cfx_idm_normal: cost, grad or gn is NULL");
-    IdmParams ip;
-    const double* TH = nullptr;
-    hipStream_t st = nullptr;
-    const int rc = idm_begin(s, s->ip, idm_check, "cfx_idm_normal", tr, true, n_id, param_ids, theta, flags,
-                             hip_stream, ip, &TH, &st);
-    if (rc != CFX_OK) return rc;
-    const int d = idm_dirs(ip);
-    return idm_normal_staged(s, n_id, cost, grad, gn, cost_per_train, flags, st,
-                             [&](double* C, double* G, double* H, double* CPT) -> int {
-                                 IDM_HIP(launch_idm_normal(s->model, s->scheme, d, ip, TH, s->d_ws, C, G, H, CPT, st));
-                                 return CFX_OK;
-                             });
-}
-
-// ------------------------------------------------------------------------------------------------------
-// multi-train fatigue-parameter identification (cfx_idfm.h): E trains share the fatigue parameters of every start.
-// The object is a cfx_idm (stream, workspace, staging buffers, error string) with the kernels' own constants.
-// ------------------------------------------------------------------------------------------------------
-struct cfx_idfm {
-    cfx_idm* core = nullptr;
-    IdfmParams fp{};
-};
-
-static const int kIdfmRowsMax = 1 + CFX_IDF_MAX_PARAMS + CFX_IDF_MAX_PARAMS * (CFX_IDF_MAX_PARAMS + 1) / 2;
-
-// Every argument check of cfx_idfm_create (no parameter list), cfx_idfm_forces and cfx_idfm_normal; tr != nullptr:
-// the host arrays too.  The train rules are cfx_idm_check's, the parameter-list rules cfx_idf_check's.
-static int idfm_check(const char* fn, int model, int scheme, int n_steps, int64_t B, int E, int P, int Nmax,
-                      bool with_ids, int32_t n_id, const int32_t* ids, int32_t* col, const cfx_idm_trains* tr,
-                      std::string& msg) {
-    const std::string f = std::string(fn) + ": ";
-    if (model < CFX_DING2003 || model > CFX_HMED2018_FATIGUE) return msg = f + "unknown model", CFX_EINVAL;
-    if (!is_fatigue(model))
-        return msg = f + "fatigue-parameter identification is only available for the fatigue models",
-               CFX_EUNSUPPORTED;
-    if (E < 1) return msg = f + "n_trains must be positive", CFX_EINVAL;
-    if (E > kMaxGridY) return msg = f + "n_trains must be <= 65535", CFX_EINVAL;
-    if (with_ids) {
-        std::string m2;
-        const int rc = idf_check(model, n_id, ids, col, m2);
-        if (rc != CFX_OK) return msg = std::string(fn) + m2.substr(7), rc;  // "cfx_idf" -> the caller's name
-    }
-    return idm_check_trains(fn, model, scheme, n_steps, B, E, P, Nmax, tr, msg);
-}
-
-extern "C" int cfx_idfm_check(int32_t model, int32_t scheme, int32_t n_steps, int64_t batch, int32_t n_trains,
-                              int32_t max_pulses, int32_t max_shooting, int32_t n_id, const int32_t* param_ids,
-                              const cfx_idm_trains* trains) {
-    int32_t col[IDF_SLOTS];
-    return idfm_check("cfx_idfm_check", model, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, true, n_id,
-                      param_ids, col, trains, g_create_error);
-}
-
-extern "C" void cfx_idfm_destroy(cfx_idfm* s) {
-    if (!s) return;
-    cfx_idm_destroy(s->core);
-    delete s;
-}
-
-extern "C" const char* cfx_idfm_last_error(const cfx_idfm* s) {
-    return s && s->core ? s->core->err.c_str() : g_create_error.c_str();
-}
-
-extern "C" int cfx_idfm_create(int32_t model, const cfx_constants* c, int32_t scheme, int32_t n_steps, int64_t batch,
-                               int32_t n_trains, int32_t max_pulses, int32_t max_shooting, int32_t device,
-                               cfx_idfm** out) {
-    if (!c || !out) return g_create_error = "cfx_idfm_create: NULL argument", CFX_EINVAL;
-    *out = nullptr;
-    int rc = idfm_check("cfx_idfm_create", model, scheme, n_steps, batch, n_trains, max_pulses, max_shooting, false,
-                        0, nullptr, nullptr, nullptr, g_create_error);
-    if (rc != CFX_OK) return rc;
-    if (!(c->tauc > 0.0)) return g_create_error = "cfx_idfm_create: tauc must be positive", CFX_EINVAL;
-    if (!(c->tau_fat > 0.0)) return g_create_error = "cfx_idfm_create: tau_fat must be positive", CFX_EINVAL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return g_create_error = "cfx_idfm_create: no HIP device available (libcfx has no CPU path)", CFX_ENODEV;
-    if (device < 0 || device >= ndev) return g_create_error = "cfx_idfm_create: bad device ordinal", CFX_ENODEV;
-    cfx_idfm* s = new cfx_idfm();
-    cfx_idm* k = s->core = new cfx_idm();
-    k->model = model;
-    k->scheme = scheme;
-    k->device = device;
-    k->B = batch;
-    k->E = n_trains;
-    k->P = max_pulses;
-    k->Nmax = max_shooting;
-    k->m = n_steps;
-    k->needs_value = is_pw(model) || is_int(model);
-    IdfmParams& fp = s->fp;
-    fp.B = batch;
-    fp.E = n_trains;
-    fp.P = max_pulses;
-    fp.Nmax = max_shooting;
-    fp.m = n_steps;
-    fp.def[IDF_AA] = c->alpha_a;
-    fp.def[IDF_AT] = c->alpha_tau1;
-    fp.def[IDF_AK] = c->alpha_km;
-    fp.def[IDF_TF] = c->tau_fat;
-    fp.inv_tauc = 1.0 / c->tauc;
-    fp.mult = c->fl * c->fv + c->fp;
-    fp.r0m1 = c->km_rest + c->r0_km_relationship - 1.0;
-    fp.tau2 = c->tau2;
-    fp.a_rest = is_pw(model) ? c->a_scale : c->a_rest;  // ding2007_with_fatigue.py:198-241: A relaxes to a_scale
-    fp.tau1_rest = c->tau1_rest;
-    fp.km_rest = c->km_rest;
-    fp.pd0 = c->pd0;
-    fp.inv_pdt = is_pw(model) ? 1.0 / c->pdt : 0.0;
-    fp.ar = c->ar;
-    fp.bs = c->bs;
-    fp.Is = c->Is;
-    fp.cr = c->cr;
-    if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking) != hipSuccess) {
-        k->stream = nullptr;
-        cfx_idfm_destroy(s);
-        return g_create_error = "cfx_idfm_create: could not create a stream on the device", CFX_EHIP;
-    }
-    if (hipMalloc((void**)&k->d_ws, (size_t)n_trains * kIdfmRowsMax * (size_t)batch * sizeof(double)) != hipSuccess) {
-        k->d_ws = nullptr;
-        cfx_idfm_destroy(s);
-        return g_create_error = "cfx_idfm_create: hipMalloc of the workspace failed", CFX_ENOMEM;
-    }
-    *out = s;
-    return CFX_OK;
-}
-
-extern "C" int cfx_idfm_forces(cfx_idfm* h, const cfx_idm_trains* tr, int32_t n_id, const int32_t* param_ids,
-                               const double* theta, double* force, double* sens, uint32_t flags, void* hip_stream) {
-    if (!h) return g_create_error = "cfx_idfm_forces: NULL handle", CFX_EINVAL;
-    cfx_idm* s = h->core;
-    if (!force) return idm_fail(s, CFX_EINVAL, "cfx_idfm_forces: force is NULL");
-    IdfmParams fp;
-    const double* TH = nullptr;
-    hipStream_t st = nullptr;
-    const int rc = idm_begin(s, h->fp, idfm_check, "cfx_idfm_forces", tr, false, n_id, param_ids, theta, flags,
-                             hip_stream, fp, &TH, &st);
-    if (rc != CFX_OK) return rc;
-    return idm_forces_staged(s, n_id, force, sens, flags, st, [&](double* F, double* S) -> int {
-        IDM_HIP(launch_idfm_sens(s->model, s->scheme, fp, TH, F, S, st));
-        return CFX_OK;
-    });
-}
-
-extern "C" int cfx_idfm_normal(cfx_idfm* h, const cfx_idm_trains* tr, int32_t n_id, const int32_t* param_ids,
-                               const double* theta, double* cost, double* grad, double* gn, double* cost_per_train,
-                               uint32_t flags, void* hip_stream) {
-    if (!h) return g_create_error = "cfx_idfm_normal: NULL handle", CFX_EINVAL;
-    cfx_idm* s = h->core;
-    if (!cost || !grad || !gn) return idm_fail(s, CFX_EINVAL, "cfx_idfm_normal: cost, grad or gn is NULL");
-    IdfmParams fp;
-    const double* TH = nullptr;
-    hipStream_t st = nullptr;
-    const int rc = idm_begin(s, h->fp, idfm_check, "cfx_idfm_normal", tr, true, n_id, param_ids, theta, flags,
-                             hip_stream, fp, &TH, &st);
-    if (rc != CFX_OK) return rc;
-    return idm_normal_staged(s, n_id, cost, grad, gn, cost_per_train, flags, st,
-                             [&](double* C, double* G, double* H, double* CPT) -> int {
-                                 IDM_HIP(launch_idfm_normal(s->model, s->scheme, fp, TH, s->d_ws, C, G, H, CPT, st));
-                                 return CFX_OK;
-                             });
-}
-#undef IDM_HIP

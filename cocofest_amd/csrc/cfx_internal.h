@@ -11,6 +11,19 @@
 // last failure of a handle-free call on this thread (cfx_last_error(NULL))
 extern thread_local std::string g_create_error;
 
+// a device buffer of n doubles that a handle grows on demand
+struct DevBuf {
+    double* p = nullptr;
+    size_t n = 0;
+};
+
+// The parameter-list checks of cfx_id_check and cfx_idf_check (cfx_api.hip), the message to msg; col[slot] = column
+// of the slot in theta (-1: not identified), ID_SLOTS / IDF_SLOTS entries.
+__attribute__((visibility("hidden"))) int id_check(int model, int32_t n_id, const int32_t* ids, int32_t* col,
+                                                   std::string& msg);
+__attribute__((visibility("hidden"))) int idf_check(int model, int32_t n_id, const int32_t* ids, int32_t* col,
+                                                    std::string& msg);
+
 // batch, layout, device and launch stream of a handle (cfx_api.hip)
 int cfx_internal_info(const cfx_handle* h, int64_t* batch, int* layout, int* device, hipStream_t* stream);
 
